@@ -8,11 +8,15 @@ prob_generator.py:434-447), from the folded condition to the latents.  value = l
 = (all ranks' B*T) / (max-over-ranks seconds per step).  Default workload = BASELINE configs[1]:
 1 utterance x 400 frames (5 s of audio), nfe=128, bf16 GEMM operands.
 
-Also reported: per-kernel-class device times (HIP events, live) with the dominant kernel's roofline
-fraction, and the oracle CPU restatement timed on the host cores (rank 0, N=1, bounded sample).
-Data: synthetic — seeded random-init weights (tests' filler), N(0,1) condition/speaker.
+A plain run sets up, warms up, times the K steps and prints the result line.  With --full it also
+reports: per-kernel-class device times (HIP events, live) with the dominant kernel's roofline
+fraction, measured peaks, the secondary rows, and the oracle CPU restatement timed on the host cores
+(rank 0, N=1, bounded sample).  --dump-outputs DIR writes the last timed step's latents to DIR/latents.npy.
+Data: synthetic — seeded random-init weights (tests' filler), N(0,1) condition/speaker; the same
+arguments give the same inputs in every run.
 
   python bench.py [--gpus N --steps K --warmup W --batch B --frames T --nfe S --dtype bf16|f32]
+                  [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -59,6 +63,14 @@ def parse():
                     help="one rank: still run the multi-rank branch (an NCCL/RCCL process group of one, device-tensor "
                          "max-over-ranks timing, efficiency fields, the configs[3] leg); implied by --config 3")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline figure: per-kernel-class "
+                         "times and rooflines, measured peaks, the CPU baseline, the secondary rows (throughput mode, "
+                         "long form, fp8, end to end) and, on the multi-rank branch, the rank-0-alone efficiency "
+                         "reference and the configs[3] leg; the --no-* switches below trim a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned to DIR/<name>.npy (float32; "
+                         "at most 64 MB, a fixed seeded sample of a larger output)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--kernel-iters", type=int, default=20, help="graph replays per kernel-class timing")
@@ -598,11 +610,12 @@ def launch_ranks(args) -> int:
     return subprocess.run(cmd, env=env).returncode
 
 
-def scaling_stats(dist, world, rank, frames_per_rank, sec, solo_sec, dev=None):
+def scaling_stats(dist, world, rank, frames_per_rank, sec, solo_sec, dev=None, with_solo=True):
     """Max-over-ranks step time (the contract's clock), every rank's own frames/s, and the efficiency of the
     whole job against N x the same per-GPU workload timed on rank 0 alone in the same process tree (the
-    other ranks idle at a barrier meanwhile).  No process group: (sec, [frames/s], None); a group of one rank
-    (--dist-single) takes the collective path below with world = 1."""
+    other ranks idle at a barrier meanwhile; timed under --full only: with_solo=False leaves the efficiency None).
+    No process group: (sec, [frames/s], None); a group of one rank (--dist-single) takes the collective path
+    below with world = 1."""
     if dist is None:
         return sec, [round(frames_per_rank / sec, 3)], None
     import torch.distributed  # noqa: F401
@@ -612,6 +625,8 @@ def scaling_stats(dist, world, rank, frames_per_rank, sec, solo_sec, dev=None):
     per[rank] = frames_per_rank / sec
     dist.all_reduce(per)
     smax = float(tt.item())
+    if not with_solo:
+        return smax, [round(float(v), 3) for v in per.cpu()], None
     solo = torch.tensor([solo_sec if rank == 0 else 0.0], dtype=torch.float64, device=dev)
     dist.all_reduce(solo)
     solo_fps = frames_per_rank / float(solo.item())
@@ -628,6 +643,25 @@ def _timed(fn, steps, sync):
         fn()
     sync()
     return (time.perf_counter() - t0) / steps
+
+
+DUMP_MAX_BYTES = 60_000_000   # --dump-outputs: array bytes of one run's files together (under 64 MB with headers)
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """--dump-outputs: write each named tensor as DIR/<name>.npy in float32 (DIR/<name>_rank<r>.npy on a
+    multi-rank job).  An output over its share of the 64 MB keeps a fixed sample instead: the flattened
+    elements at sorted indices drawn without replacement by numpy's default_rng(0), the same for every
+    run of that shape, so two builds dump the same positions."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    cap = DUMP_MAX_BYTES // (4 * max(1, world) * max(1, len(arrays)))   # float32 elements per file
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).contiguous().numpy()
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
 
 
 def plumbing(args, rank, world):
@@ -660,7 +694,7 @@ def plumbing(args, rank, world):
         for _ in range(max(1, args.warmup)):
             step()
         solo = None
-        if world > 1:
+        if world > 1 and args.full:
             dist.barrier()
             if rank == 0:
                 solo = _timed(step, args.steps, nosync)
@@ -668,7 +702,7 @@ def plumbing(args, rank, world):
         sec = _timed(step, args.steps, nosync)
         if world > 1:
             dist.barrier()
-        sec, per_rank, eff = scaling_stats(dist if world > 1 else None, world, rank, B * T, sec, solo)
+        sec, per_rank, eff = scaling_stats(dist if world > 1 else None, world, rank, B * T, sec, solo, with_solo=args.full)
     out = res["out"]
     _, label = workload_label(args, world)
     line = {"metric": "latent frames/s (plumbing: CPU torch path over gloo)", "value": round(world * B * T / sec, 3),
@@ -755,7 +789,7 @@ def main():
             out = step()
         torch.cuda.synchronize()
         solo = None
-        if dist:  # the N = 1 reference of the efficiency figure: rank 0 alone, the other ranks idle
+        if dist and args.full:  # the N = 1 reference of the efficiency figure: rank 0 alone, the other ranks idle
             dist.barrier()
             if rank == 0:
                 solo = _timed(step, args.steps, sync)
@@ -777,8 +811,50 @@ def main():
         if dist:
             dist.barrier()
         sec = (t1 - t0) / args.steps
-        sec, per_rank, eff = scaling_stats(dist, world, rank, B * T, sec, solo, dev)
+        sec, per_rank, eff = scaling_stats(dist, world, rank, B * T, sec, solo, dev, with_solo=args.full)
         finite = bool(torch.isfinite(out).all().item())
+        if args.dump_outputs:
+            # what a caller of the timed path holds after its own synchronisation: the last timed solve,
+            # once the handle has checked that solve's persistent launch (settle, as Flamed.sample_batch does)
+            hip.settle(block=True)
+            torch.cuda.synchronize()
+            dump_outputs(args.dump_outputs, {"latents": out}, rank, world)
+
+    audio_s = T * 200 / 16000.0
+    value = world * B * T / sec
+    cfg_i, label = workload_label(args, world)
+    label += " (one persistent launch per solve)" if persist_runs >= args.steps else " (hipGraph Euler solve)"
+    line = {
+        "metric": "latent frames/s (RTF at nsteps-denoiser=128)", "value": round(value, 2),
+        "unit": "latent frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(sec * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": args.dtype, "data": "synthetic (seeded random-init weights, N(0,1) condition/speaker)",
+        "config": {"workload": label, "baseline_config": cfg_i,
+                   "batch_per_gpu": B, "frames": T, "nfe": nfe, "global_batch": world * B,
+                   "parallelism": f"utterance-sharded x{world} (no collectives)"},
+        "per_rank_frames_per_s": per_rank, "scaling_detail": eff,
+        "rtf_denoiser": round(sec / audio_s, 6),
+        "persistent": {"runs": persist_runs, "solves": args.steps,
+                       "launch_ms": [round(x, 3) for x in pms] if pms else None},
+        "finite": finite,
+        "full": bool(args.full),
+    }
+    if args.full:
+        line.update(full_measurements(args, pg, hip, dev, dist, world, rank, cfg, xt0, ts, spk, noise, cond, spk_cpu,
+                                      persist_runs, pms))
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if dist:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_measurements(args, pg, hip, dev, dist, world, rank, cfg, xt0, ts, spk, noise, cond, spk_cpu, persist_runs, pms):
+    """--full: what the benchmark measures beside its headline figure, after the timed steps and on the same
+    handle and inputs; returns the extra fields of the result line."""
+    from flamed import _native as nat
+    B, T, nfe, C, H, NB = args.batch, args.frames, args.nfe, cfg["target_dim"], cfg["hidden_dim"], cfg["n_layers"]
+    with torch.inference_mode():
         configs3 = None
         if dist and not args.no_configs3 and B != CONFIGS[3]["batch"]:
             configs3 = configs3_leg(pg, dev, dist, world, rank, args, C)
@@ -917,37 +993,17 @@ def main():
         except Exception as e:
             secondary["long_form"] = {"error": f"{type(e).__name__}: {e}"}
 
-    audio_s = T * 200 / 16000.0
-    value = world * B * T / sec
-    cfg_i, label = workload_label(args, world)
-    label += " (one persistent launch per solve)" if persist_runs >= args.steps else " (hipGraph Euler solve)"
-    line = {
-        "metric": "latent frames/s (RTF at nsteps-denoiser=128)", "value": round(value, 2),
-        "unit": "latent frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(sec * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": args.dtype, "data": "synthetic (seeded random-init weights, N(0,1) condition/speaker)",
-        "config": {"workload": label, "baseline_config": cfg_i,
-                   "batch_per_gpu": B, "frames": T, "nfe": nfe, "global_batch": world * B,
-                   "parallelism": f"utterance-sharded x{world} (no collectives)"},
-        "per_rank_frames_per_s": per_rank, "scaling_detail": eff, "configs3": configs3,
-        "rtf_denoiser": round(sec / audio_s, 6),
+    return {
+        "configs3": configs3,
         "roofline": roof,
         "kernels": [{k: v for k, v in kk.items() if k not in ("bytes", "flops")} for kk in kernels],
         "kernel_timing": "graph-of-launches path (B > 1, and the B = 1 fallback): in-graph per-launch cost "
                          "(4-step graph with the class doubled minus as captured, HIP events)",
-        "persistent": {"runs": persist_runs, "solves": args.steps,
-                       "launch_ms": [round(x, 3) for x in pms] if pms else None},
         "step_us_graph": round(ms[N_CLASSES] * 1e3, 2),
         "cpu_baseline": cpu,
         "peaks": {"hbm_spec_GBps": HBM_PEAK_GBS, "bf16_dense_spec_TFs": MFMA_PEAK_TFS["bf16"], **(peaks or {})},
-        "finite": finite,
         "secondary": secondary,
     }
-    if rank == 0:
-        print(json.dumps(line), flush=True)
-    if dist:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -45,7 +45,7 @@ def test_world_mismatch_rejected():
 def test_launcher_world2_configs3_labels():
     """a multi-rank run is labelled as the configs[3] layout with its global batch, every
     rank's own frames/s and the efficiency against rank 0 running the same per-GPU workload alone."""
-    line = _run(["--gpus", "2", "--plumbing", "--config", "3", "--batch", "4", "--frames", "12", "--nfe", "2",
+    line = _run(["--gpus", "2", "--plumbing", "--full", "--config", "3", "--batch", "4", "--frames", "12", "--nfe", "2",
                  "--steps", "1", "--warmup", "1"])
     cfg = line["config"]
     assert "configs[3]" in cfg["workload"] and "utterance-sharded over 2 GPU" in cfg["workload"], cfg["workload"]

@@ -16,7 +16,7 @@ REPO = os.path.dirname(PKG)
 
 
 def test_bench_single_rank_dist_branch():
-    args = ["--dist-single", "--steps", "1", "--warmup", "1", "--no-secondary", "--no-cpu-baseline", "--no-peaks",
+    args = ["--full", "--dist-single", "--steps", "1", "--warmup", "1", "--no-secondary", "--no-cpu-baseline", "--no-peaks",
             "--kernel-iters", "2"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py")] + args, capture_output=True, text=True,

@@ -14,7 +14,7 @@ cd /tmp
 ( while true; do date >> $OUT/heartbeat; sleep 50; done ) &
 HB=$!
 trap "kill $HB 2>/dev/null" EXIT
-BENCH="python3 $ROOT/bench.py --no-cpu-baseline --no-secondary --no-peaks --coop 0 --steps 1 --warmup 1 --kernel-iters 2 $*"
+BENCH="python3 $ROOT/bench.py --full --no-cpu-baseline --no-secondary --no-peaks --coop 0 --steps 1 --warmup 1 --kernel-iters 2 $*"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o run -- $BENCH > $OUT/kt.log 2>&1 || { echo "kernel trace failed"; tail -5 $OUT/kt.log; exit 1; }
 i=0
 for grp in "SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_INSTS_VALU_MFMA_MOPS_F8 SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE GRBM_COUNT" \

@@ -95,7 +95,7 @@ def main():
     bench = os.path.join(a.run_dir, "bench.json")
     with open(a.out_prefix + "_kernels.md", "w") as fo:
         fo.write(f"# rocprofv3 summary — {os.path.basename(a.out_prefix)} (B={a.batch}, T={a.frames}, {a.dtype})\n\n")
-        fo.write("Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --no-secondary --no-peaks"
+        fo.write("Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-secondary --no-peaks"
                  " --coop 0 --steps 2 --warmup 1`; PMC: separate `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes of the same"
                  " bench.  The profiled persistent launch is a plain launch (`--coop 0`: rocprofv3's teardown faults after"
                  " cooperative launches, README \"Known issues\"); the bench's own HIP-event timing of the shipped"
