@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from _common import orc, rel_l2, t32
+from _rowprofile import assert_row_profile, memo, solve_floor, velocity_floor
 from test_denoiser_gpu import _prob_gen
 
 pytestmark = pytest.mark.gpu
@@ -74,7 +75,7 @@ def cfg1_ref(pg_bf16):
 
 def test_cfg1_solve_128_bf16(pg_bf16, cfg1_ref):
     """configs[1] as benchmarked: default bf16 path (B = 1: the persistent solve, persist.hip; LayerNorm fold)."""
-    pg, _ = pg_bf16
+    pg, sd = pg_bf16
     x0, spk, ref = cfg1_ref
     out = _solve(pg, x0, spk, 128)
     e = rel_l2(out, ref)
@@ -83,6 +84,10 @@ def test_cfg1_solve_128_bf16(pg_bf16, cfg1_ref):
     assert torch.isfinite(out).all()
     assert e < BF16_SOLVE
     assert amax < 0.05  # absolute bound on the folded default path: measured 1.5e-2 with |ref|max 7.4
+    # per-frame profile (the other long solves keep their global bars: a 128-step emulated floor costs as much as
+    # the oracle solve itself; this one is shared with test_persist_gpu.py, same inputs)
+    floor = memo("cfg1_128", lambda: solve_floor(sd, x0, spk, 128))
+    assert_row_profile(out, ref, floor, "configs[1] bf16 128 steps")
 
 
 def test_cfg1_solve_128_f32(pg_f32, cfg1_ref):
@@ -133,6 +138,7 @@ def test_cfg2_velocity_full_size(pg_bf16, cfg2):
     e = rel_l2(v, ref)
     print(f"configs[2] B=64 T=400 bf16 velocity rel-L2 {e:.3e}")
     assert e < BF16_VEL
+    assert_row_profile(v, ref, velocity_floor(sd, x0, t, spk), "configs[2] B=64 T=400 velocity")  # floor: 6 utterances
 
 
 def test_cfg2_solve_128(pg_bf16, cfg2):

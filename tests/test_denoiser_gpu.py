@@ -6,6 +6,9 @@ Tolerances (rel-L2 = ||a-b|| / ||b||):
   * bf16 mode (bf16 GEMM operands, fp32 accumulate/residual/norms): velocity <= 8e-3 (~2x the measured
     3.7e-3 .. 3.9e-3), short solves <= 6e-3 (SURVEY.md §8(c) allows 2e-2; the reference itself under
     CPU bf16 autocast drifts to 8.5e-3 velocity rel-L2).  128/256-step solves: test_configs_gpu.py.
+  * bf16 mode, per frame: no frame further from the oracle than 2x the worst frame of a bf16 emulation of the
+    oracle on the same input (_rowprofile.assert_row_profile) -- the global norm above divides an error confined
+    to a few frames (a tile, chunk or utterance edge) by sqrt(frames).
 """
 import numpy as np
 import pytest
@@ -13,6 +16,7 @@ import torch
 import yaml
 
 from _common import golden, seeded, t32, rel_l2, orc, PKG
+from _rowprofile import assert_row_profile, emulated_prob_sample, solve_floor, velocity_floor
 
 pytestmark = pytest.mark.gpu
 
@@ -69,7 +73,7 @@ def test_velocity_ragged_shapes_f32(B, T, pg_f32):
 
 @pytest.mark.parametrize("mode,tol", [("f32", 1e-4), ("bf16", BF16_SOLVE)])
 def test_prob_sample_golden(mode, tol, pg_f32, pg_bf16):
-    pg, _ = pg_f32 if mode == "f32" else pg_bf16
+    pg, sd = pg_f32 if mode == "f32" else pg_bf16
     g = golden("prob_sample")
     lens = t32(g["lens"])
     T = g["cond"].shape[2]
@@ -80,6 +84,11 @@ def test_prob_sample_golden(mode, tol, pg_f32, pg_bf16):
                         temperature=float(g["temperature"])).cpu()
     assert lat.shape == g["latents"].shape
     assert rel_l2(lat, g["latents"]) < tol
+    if mode == "bf16":  # per-frame profile (padded frames included); the f32 bar already resolves single frames
+        torch.manual_seed(int(g["rng_seed"]))
+        noise = torch.randn((lat.shape[0], T, lat.shape[1]))  # the draw ProbGenerator.sample makes (prob_generator.py:440)
+        floor = emulated_prob_sample(sd, t32(g["cond"]), t32(g["spk"]), mask, int(g["nfe"]), float(g["temperature"]), noise)
+        assert_row_profile(lat.transpose(1, 2), t32(g["latents"]).transpose(1, 2), floor, "prob_sample golden bf16")
 
 
 def test_solve_graph_equals_eager_and_oracle(pg_f32):
@@ -152,6 +161,7 @@ def test_split_k_solve_bf16(target, mx, pg_bf16):
     assert rel_l2(a, base) < 5e-3  # bf16 re-rounding of U after a different fp32 summation order
     ref = orc.euler_solve(sd, x0, spk, nfe)
     assert rel_l2(a, ref) < BF16_SOLVE
+    assert_row_profile(a, ref, solve_floor(sd, x0, spk, nfe), f"split-K target {target} max {mx}")
 
 
 @pytest.mark.parametrize("per_frame_t", [False, True])
@@ -176,6 +186,9 @@ def test_velocity_large_m_bf16(per_frame_t, pg_bf16):
         nat.check(L.flamed_tune(b"big", 1), "tune")
     assert rel_l2(v_big, ref) < BF16_VEL
     assert rel_l2(v_fused, ref) < BF16_VEL
+    floor = velocity_floor(sd, x, t, c)
+    assert_row_profile(v_big, ref, floor, f"large-M 128x128 per_frame_t={per_frame_t}")
+    assert_row_profile(v_fused, ref, floor, f"large-M fused (big 0) per_frame_t={per_frame_t}")
 
 
 @pytest.mark.parametrize("knobs,B,T", [
@@ -215,6 +228,10 @@ def test_velocity_tuning_paths_bf16(knobs, B, T, pg_bf16):
         for k in knobs:
             nat.check(L.flamed_tune(k.encode(), defaults[k]), "tune")
     assert rel_l2(v_hip, ref) < BF16_VEL
+    # x16 cases (all on the large-M path, where the knob acts): the floor rounds the residual stream and the
+    # depthwise output too
+    floor = velocity_floor(sd, x, t, c, x16=bool(knobs.get("x16")))
+    assert_row_profile(v_hip, ref, floor, f"tuning {knobs} B={B} T={T}")
 
 
 @pytest.mark.parametrize("B,T,per_frame_t", [(1, 400, False), (2, 300, True), (17, 500, False), (4, 400, False)])
@@ -269,11 +286,13 @@ def test_velocity_path_boundaries_bf16(B, T, pg_bf16):
     c = torch.randn(B, 256, generator=g)
     t = torch.tensor([[0.3]])
     ref = orc.denoiser_forward(sd, x, t, c)
-    e = rel_l2(_vel(pg, x, t, c), ref)
+    v = _vel(pg, x, t, c)
+    e = rel_l2(v, ref)
     print(f"B={B} T={T} bf16 velocity rel-L2 {e:.3e}")
     # T <= 2: GroupNorm(H, H) over <= 2 frames per channel amplifies the bf16 rounding of the GEMM
     # operands (measured 1.2e-2 at B=1, T=2); SURVEY.md §8(c)'s bf16 bar 2e-2 applies there
     assert e < (BF16_VEL if T > 2 else 2e-2)
+    assert_row_profile(v, ref, velocity_floor(sd, x, t, c), f"path boundary B={B} T={T}")  # the floor adapts at T <= 2
 
 
 @pytest.mark.parametrize("mode,tol", [("f32", 1e-5), ("bf16", 8e-3)])
@@ -368,3 +387,47 @@ def test_solve_in_parts_equals_whole(pg_bf16):
                                        1, 1, nfe, nat.stream_ptr(DEV)) == 1001  # off a chunk boundary
         torch.cuda.synchronize()
     assert torch.equal(x.cpu(), whole)
+
+
+_launch_refs = {}
+
+
+def _launch_ref(sd, B, T):
+    """Inputs, oracle velocity and bf16-emulation floor of one shape, computed once for the cases that share it."""
+    if (B, T) not in _launch_refs:
+        g = torch.Generator().manual_seed(B * 1009 + T)
+        x = torch.randn(B, T, 256, generator=g)
+        c = torch.randn(B, 256, generator=g)
+        t = torch.tensor([[0.45]])
+        _launch_refs[(B, T)] = (x, t, c, orc.denoiser_forward(sd, x, t, c), velocity_floor(sd, x, t, c))
+    return _launch_refs[(B, T)]
+
+
+@pytest.mark.parametrize("knobs,B,T", [
+    ({}, 5, 333), ({}, 3, 513), ({}, 13, 100), ({}, 16, 100), ({"g8p_rows": 0}, 46, 250), ({"g8p_rows": 11500}, 46, 250),
+    ({}, 2, 130), ({}, 1, 319), ({}, 1, 9)])
+def test_launch_edge_profiles(knobs, B, T, pg_bf16):
+    """The per-frame profile of one bf16 velocity where tile edges fall inside utterances and utterance edges
+    inside tiles.  (5, 333): 1,665 rows, 128 x 128 tiles, whole-utterance depthwise + GroupNorm kernel; (3, 513):
+    dwgn falls back to the chunked pass; (13, 100): 1,300 rows stay under the large-M threshold (1,536), so it is
+    the small-M tiles that span utterance edges there -- (16, 100), 1,600 rows, is the shape where a 128-row tile
+    spans two or three utterances; (46, 250): 11,500 rows, the smallest count the 256 x 256 8-phase dispatch accepts
+    (180 tiles; a 256-row tile spans two utterances; subset floor) -- g8p_rows 0 switches the 8-phase tiles OFF
+    (launch_big: g8 > 0), so that case is the 128 x 128 ring at this size and g8p_rows 11500 is the 8-phase one;
+    (2, 130) and (1, 319): small-M tiles, dwgn_small; (1, 9): under one tile and under the depthwise halo (the
+    persistent solve takes no T < 16)."""
+    from flamed import _native as nat
+    pg, sd = pg_bf16
+    x, t, c, ref, floor = _launch_ref(sd, B, T)
+    L = nat.lib()
+    try:
+        for k, v in knobs.items():
+            nat.check(L.flamed_tune(k.encode(), v), "tune")
+        v_hip = _vel(pg, x, t, c)
+    finally:
+        for k in knobs:
+            nat.check(L.flamed_tune(k.encode(), {"g8p_rows": 12800}[k]), "tune")
+    e = rel_l2(v_hip, ref)
+    print(f"launch edge {knobs} B={B} T={T}: velocity rel-L2 {e:.3e}")
+    assert e < BF16_VEL
+    assert_row_profile(v_hip, ref, floor, f"launch edge {knobs} B={B} T={T}")

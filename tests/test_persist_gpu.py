@@ -6,7 +6,10 @@ Checks: the solve really ran persistently (flamed_den_persist_info), against the
 bf16 solve tolerance of the launch path (rel-L2 <= 6e-3 and max|d| < 0.05 at configs[1]), at edge lengths
 (T = 16: most groups empty; 40 / 131 / 257: partial tiles; 512: every group full), against the launch path
 (same bf16 operands, different fp32 reduction order: rel-L2 <= 4e-3), bitwise determinism, and parts
-[0, G) + [G, nfe) equal to the whole (the fp32 state passes through xt exactly).
+[0, G) + [G, nfe) equal to the whole (the fp32 state passes through xt exactly).  Every comparison with the oracle
+also holds each frame to 2x the worst frame of the oracle's bf16 emulation (_rowprofile.assert_row_profile), at the
+shapes of the tests above and at the smallest shapes with a row-group, chunk, tile or utterance edge
+(test_persist_edge_profiles), and through ProbGenerator.sample on masked ragged batches (test_sample_ragged_profile).
 """
 import contextlib
 import os
@@ -15,6 +18,7 @@ import pytest
 import torch
 
 from _common import orc, rel_l2
+from _rowprofile import assert_row_profile, emulated_prob_sample, memo, solve_floor
 from test_denoiser_gpu import _prob_gen
 
 pytestmark = pytest.mark.gpu
@@ -54,6 +58,16 @@ def _solve(pg, x0, spk, nfe):
         return hip.solve(x0.to(DEV), ts, spk.to(DEV), nfe).cpu()
 
 
+def _oracle(sd, x0, spk, nfe):
+    """One-utterance oracle solves (equal lengths: no padding coupling), concatenated to (B, T, C)."""
+    torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
+    return torch.cat([orc.euler_solve(sd, x0[u:u + 1], spk[u:u + 1], nfe) for u in range(x0.shape[0])])
+
+
+def _errs(out, ref):
+    return [rel_l2(out[u:u + 1], ref[u:u + 1]) for u in range(ref.shape[0])]
+
+
 def _runs(pg):
     if pg.denoiser.hip().handle is None:  # no solve on this module yet (e.g. a -k selection)
         return 0
@@ -80,6 +94,9 @@ def test_persist_cfg1_vs_oracle_and_launch_path(pgb):
     assert torch.isfinite(out).all()
     assert e < BF16_SOLVE and amax < 0.05
     assert el < 4e-3
+    floor = memo("cfg1_128", lambda: solve_floor(sd, x0, spk, 128))
+    assert_row_profile(out, ref, floor, "persistent configs[1] 128 steps")
+    assert_row_profile(launch, ref, floor, "launch path configs[1] 128 steps")
 
 
 @pytest.mark.parametrize("T", [16, 40, 131, 257, 512])
@@ -94,6 +111,7 @@ def test_persist_lengths_vs_oracle(pgb, T):
     e = rel_l2(out, ref)
     print(f"persistent T={T} 8 steps: vs oracle rel-L2 {e:.3e}")
     assert e < BF16_SOLVE
+    assert_row_profile(out, ref, solve_floor(sd, x0, spk, 8), f"persistent T={T}")
 
 
 def test_persist_deterministic_and_parts(pgb):
@@ -407,9 +425,11 @@ def test_persist_multi_counter_groupnorm(pgb, B, T, part):
         with knob("persist_opt", base ^ 512, PERSIST_DEFAULT):
             b = _solve(pg, x0, spk, 8)
         assert _runs(pg) == r0 + 1
-    errs = [rel_l2(b[u:u + 1], orc.euler_solve(sd, x0[u:u + 1], spk[u:u + 1], 8)) for u in range(B)]
+    ref = _oracle(sd, x0, spk, 8)
+    errs = _errs(b, ref)
     print(f"persistent B={B} T={T} counter GroupNorm: vs oracle per utterance max {max(errs):.3e}")
     assert torch.isfinite(b).all() and torch.equal(a, b) and max(errs) < BF16_SOLVE
+    assert_row_profile(b, ref, solve_floor(sd, x0, spk, 8), f"persistent counter GroupNorm B={B} T={T} part={part}")
 
 
 @pytest.mark.parametrize("B,T", [(2, 200), (4, 100), (8, 64), (2, 37)])
@@ -429,9 +449,11 @@ def test_persist_multi_utterance(pgb, B, T):
             launch = _solve(pg, x0, spk, 8)
     assert torch.isfinite(out).all()
     el = rel_l2(out, launch)
-    errs = [rel_l2(out[b:b + 1], orc.euler_solve(sd, x0[b:b + 1], spk[b:b + 1], 8)) for b in range(B)]
+    ref = _oracle(sd, x0, spk, 8)
+    errs = _errs(out, ref)
     print(f"persistent B={B} T={T} 8 steps: vs oracle per utterance max {max(errs):.3e}; vs launch path {el:.3e}")
     assert max(errs) < BF16_SOLVE and el < 4e-3
+    assert_row_profile(out, ref, solve_floor(sd, x0, spk, 8), f"persistent multi-utterance B={B} T={T}")
 
 
 @pytest.mark.parametrize("B,T", [(3, 256), (3, 100), (5, 64), (6, 100), (7, 48)])
@@ -454,9 +476,11 @@ def test_persist_padded_batch(pgb, B, T):
         launch = _solve(pg, x0, spk, 8)
     assert torch.isfinite(a).all() and torch.equal(a, full[:B])
     el = rel_l2(a, launch)
-    errs = [rel_l2(a[u:u + 1], orc.euler_solve(sd, x0[u:u + 1], spk[u:u + 1], 8)) for u in range(B)]
+    ref = _oracle(sd, x0, spk, 8)
+    errs = _errs(a, ref)
     print(f"persistent padded B={B} (as {Bp}) T={T}: vs launch path {el:.3e}, vs oracle per utterance max {max(errs):.3e}")
     assert el < 4e-3 and max(errs) < BF16_SOLVE
+    assert_row_profile(a, ref, solve_floor(sd, x0, spk, 8), f"persistent padded B={B} T={T}")
 
 
 @pytest.mark.parametrize("B,T", [(1, 520), (1, 1000), (1, 2400), (2, 400), (4, 300), (2, 1111),
@@ -479,9 +503,11 @@ def test_persist_multi_chunk(pgb, B, T):
         launch = _solve(pg, x0, spk, 8)
     assert torch.isfinite(a).all() and torch.equal(a, b)
     el = rel_l2(a, launch)
-    errs = [rel_l2(a[u:u + 1], orc.euler_solve(sd, x0[u:u + 1], spk[u:u + 1], 8)) for u in range(B)]
+    ref = _oracle(sd, x0, spk, 8)
+    errs = _errs(a, ref)
     print(f"persistent multi-chunk B={B} T={T}: vs launch path {el:.3e}, vs oracle per utterance max {max(errs):.3e}")
     assert el < 4e-3 and max(errs) < BF16_SOLVE
+    assert_row_profile(a, ref, solve_floor(sd, x0, spk, 8), f"persistent multi-chunk B={B} T={T}")
 
 
 @pytest.mark.parametrize("B,T", [(1, 1000), (2, 1111), (4, 800)])
@@ -519,6 +545,85 @@ def test_persist_row_partition(pgb, B, T):
     assert _runs(pg) == r0 + 2
     assert torch.isfinite(a).all() and torch.isfinite(b).all()
     d = rel_l2(a, b)
-    errs = [rel_l2(a[u:u + 1], orc.euler_solve(sd, x0[u:u + 1], spk[u:u + 1], 8)) for u in range(B)]
+    ref = _oracle(sd, x0, spk, 8)
+    errs = _errs(a, ref)
     print(f"row partition B={B} T={T}: tiles vs shares {d:.3e}, vs oracle per utterance max {max(errs):.3e}")
     assert d < 4e-3 and max(errs) < BF16_SOLVE
+    floor = solve_floor(sd, x0, spk, 8)
+    assert_row_profile(a, ref, floor, f"row partition default B={B} T={T}")
+    assert_row_profile(b, ref, floor, f"row partition flipped B={B} T={T}")
+
+
+_edge_refs = {}
+
+
+def _edge_ref(sd, B, T, nfe=4):
+    """Inputs, oracle solve and bf16-emulation floor of one edge shape, computed once for both row partitions."""
+    if (B, T) not in _edge_refs:
+        torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
+        x0, spk = _inputs(800 + 16 * T + B, B, T)
+        _edge_refs[(B, T)] = (x0, spk, orc.euler_solve(sd, x0, spk, nfe), solve_floor(sd, x0, spk, nfe))
+    return _edge_refs[(B, T)]
+
+
+@pytest.mark.parametrize("part", [0, 2])
+@pytest.mark.parametrize("B,T", [
+    (1, 16), (1, 33), (1, 97), (1, 120), (1, 121), (1, 127), (1, 128), (1, 129), (1, 513), (1, 1025),
+    (2, 65), (4, 17), (4, 129), (8, 16), (8, 65), (3, 33), (5, 17)])
+def test_persist_edge_profiles(pgb, B, T, part):
+    """The per-frame profile of a 4-step persistent solve at the smallest shapes where the row-group, chunk, tile
+    and utterance edges exist, under both row partitions (part = persist_opt bit 2 flipped: equal ceil(T / groups)
+    shares vs whole 16-row tiles).  B = 1 (8 groups): T = 16 one tile, seven groups empty; 33: the 15-row depthwise
+    halo spans several groups; 97: share 13 below the halo, the tile partition leaves a group empty; 120 / 121:
+    share = halo, halo + 1; 127 / 128 / 129: the tile-partition edge; 513: first two-chunk shape (share 65; five
+    tiles = 80 rows); 1025: three chunks.  B > 1: utterance edge = group edge -- (4, 129) and (8, 65) put a one-row
+    second chunk there; (3, 33) and (5, 17) run padded to 4 / 8 utterances.
+    The dispatcher takes no utterance under 16 frames (persist_eligible: T < 16), so the one-tile shape is T = 16,
+    not 9, and the shortest 8-utterance batch (8, 16), not (8, 2); T = 9 and T = 2 run on the launch path
+    (test_launch_edge_profiles, test_velocity_path_boundaries_bf16)."""
+    pg, sd = pgb
+    x0, spk, ref, floor = _edge_ref(sd, B, T)
+    r0 = _runs(pg)
+    with knob("persist_opt", PERSIST_DEFAULT ^ part, PERSIST_DEFAULT):
+        out = _solve(pg, x0, spk, 4)
+    assert _runs(pg) == r0 + 1, "the edge shape did not take the persistent path"
+    e = rel_l2(out, ref)
+    print(f"persistent edge B={B} T={T} part={part}: rel-L2 {e:.3e}")
+    assert e < BF16_SOLVE
+    assert_row_profile(out, ref, floor, f"persistent edge B={B} T={T} part={part}")
+
+
+def _ragged(pg, sd, lens, persist):
+    """ProbGenerator.sample on a padded batch (mask True = valid) against orc.prob_sample with the same noise:
+    global bf16 solve bar and the per-frame profile over every frame, padded ones included (the denoiser never
+    sees the mask: padded frames carry noise * temperature + the masked fold and are processed like real ones)."""
+    B, T, nfe, temp = len(lens), max(lens), 8, 0.3
+    g = torch.Generator().manual_seed(sum(lens))
+    cond = torch.randn(B, 6, T, 384, generator=g)
+    spk = torch.randn(B, C, generator=g)
+    mask = (torch.arange(T)[None, :] < torch.tensor(lens)[:, None]).unsqueeze(-1)
+    torch.manual_seed(17)
+    noise = torch.randn((B, T, C))  # the draw ProbGenerator.sample makes from the global CPU RNG
+    torch.manual_seed(17)
+    r0 = _runs(pg)
+    with knob("persist", persist, 1), torch.inference_mode():
+        lat = pg.sample(cond.to(DEV), spk.to(DEV), mask.to(DEV), nfe=nfe, temperature=temp).cpu()
+    assert _runs(pg) == r0 + persist, "ProbGenerator.sample took the other solve path"
+    torch.set_num_threads(max(1, min(16, os.cpu_count() or 1)))
+    ref = orc.prob_sample(sd, cond, spk, mask, nfe=nfe, temperature=temp, noise=noise).transpose(1, 2)
+    floor = emulated_prob_sample(sd, cond, spk, mask, nfe, temp, noise)
+    out = lat.transpose(1, 2)
+    e = rel_l2(out, ref)
+    print(f"ragged sample lens {lens} persist={persist}: rel-L2 {e:.3e}")
+    assert lat.shape == (B, C, T) and e < BF16_SOLVE
+    assert_row_profile(out, ref, floor, f"ragged sample lens {lens} persist={persist}")
+
+
+@pytest.mark.parametrize("path", ["persistent", "launch", "launch_1600"])
+def test_sample_ragged_profile(pgb, path):
+    """VERDICT's ragged-batch parity at small shapes: lengths 100 / 77 / 55 / 31 padded to 100 (the utterance edge
+    inside a row group, the masked fold feeding the solve) on the persistent path and on the graph of launches,
+    and 400 / 301 / 207 / 90 (1,600 rows: the large-M path) on the graph of launches."""
+    pg, sd = pgb
+    lens = [400, 301, 207, 90] if path == "launch_1600" else [100, 77, 55, 31]
+    _ragged(pg, sd, lens, 1 if path == "persistent" else 0)
