@@ -1338,6 +1338,19 @@ __global__ void conv3_combine_kernel(const float* __restrict__ Y, const float* _
   }
 }
 
+// Two-stage second-order solvers (flamed_den_solve_rk2) on the launch path: the state update behind each velocity
+// evaluation, xo = xb + c1 (y - xb) + g v.  First evaluation of a step (y null): the stage state xo = y = xb + (a dt) v;
+// second: the step itself, xo = xb in place, g = c2 dt.  Explicit roundings, so the eager and the captured solve agree
+// bitwise (no contraction into FMAs).
+__global__ void rk2_update_kernel(const float* xb, const float* y, const float* __restrict__ v, float* xo, size_t n, float c1,
+                                  float g) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n) return;
+  const float b = xb[idx];
+  const float base = y ? __fadd_rn(b, __fmul_rn(c1, __fsub_rn(y[idx], b))) : b;
+  xo[idx] = __fadd_rn(base, __fmul_rn(g, v[idx]));
+}
+
 // Fused solve (small M, graph path): the conv_out tap combine + Euler update of step s-1 is computed
 // inside step s's proj_in A loader, exactly as conv3_combine_kernel does it (same fp32 operation order,
 // so the solve stays bitwise equal to the eager one):  x_s = x_{s-1} + dt * (b + Y1[t] + Y0[t-1] +
@@ -1763,6 +1776,7 @@ struct Den {
   int qprobe_busy = 0;  // probe pairs that neither ran concurrently nor back-to-back (the device was busy): not parked
   int* qprobe = nullptr;                       // probe flag + result words
   int g_B = -1, g_T = -1, g_nfe = -1, g_epoch = -1;
+  double g_a = 0.0;  // stage parameter of the cached graph's solver (0: Euler)
   const void *g_xt = nullptr, *g_mods = nullptr, *g_ws = nullptr;
   int* ctr = nullptr;  // device Euler step counter for graph replay
   int* scnt = nullptr;  // split-K tile counters (zeroed at load; every launch leaves them zero)
@@ -1779,7 +1793,7 @@ struct Den {
   bool pbroken = false;      // kPersistRetry launches failed on this handle: launch path from then on
   int pruns = 0;             // persistent launches enqueued
   int ppath = -1;            // path of the solve whose step 0 ran last: 1 persistent, 0 graph of launches
-  int ppath_key[3] = {-1, -1, -1};  // its (B, T, nfe)
+  int ppath_key[3] = {-1, -1, -1};  // its (B, T, nfe); a two-stage solve records -nfe (it has no later parts)
   // the most recent uncaptured persistent launches, a ring: HIP events around the kernel ([0], [1]: device time) and
   // behind the async copies that follow it ([2]), and each launch's own error word (pinned; 0 = the launch
   // succeeded), so a caller can ask after one launch without waiting (flamed_den_persist_query)
@@ -1854,7 +1868,8 @@ struct DenWs {
   size_t SLn;
   bf16* A16;   // large-M bf16 path: normalised A operand rows, M x H (null otherwise)
   bf16* XA;    // LayerNorm fold: X * alpha_next rows (bf16 handles), M x H
-  float* XP;   // fused solve: second Euler-state buffer, M x C
+  float* XP;   // fused solve: second Euler-state buffer, M x C (two-stage solvers: the stage state y)
+  float* XV;   // two-stage solvers: the velocity of the current evaluation, M x C
 };
 
 // split-K slab capacity: 32 x 64 tiles of the widest GEMM (max(H, 3C) columns) x 4 slices, small M only
@@ -1883,11 +1898,12 @@ static size_t den_ws_layout(const Den* d, int B, int T, void* base, DenWs* w) {
   const size_t sl = den_slab_floats(d, B, T);
   const size_t a16 = (d->dt == FLAMED_BF16 && M >= (size_t)tn().big_min_rows) ? 2 * M * d->H : 0;  // large-M path range
   const size_t xa = d->fold ? 2 * M * d->H : 0;
-  size_t sizes[12] = {xs * M * d->H, 8 * M * NTmax, 8 * M * NTmax, xs * M * d->H, es * M * d->H, 12 * B * TS * d->H,
-                      8 * (size_t)B * d->H, 12 * M * d->C, 4 * sl, a16, xa, 4 * M * d->C};
+  // (XV last: every other buffer keeps the offset it had before the two-stage solvers)
+  size_t sizes[13] = {xs * M * d->H, 8 * M * NTmax, 8 * M * NTmax, xs * M * d->H, es * M * d->H, 12 * B * TS * d->H,
+                      8 * (size_t)B * d->H, 12 * M * d->C, 4 * sl, a16, xa, 4 * M * d->C, 4 * M * d->C};
   size_t off = 0;
-  void* ptrs[12];
-  for (int i = 0; i < 12; ++i) {
+  void* ptrs[13];
+  for (int i = 0; i < 13; ++i) {
     ptrs[i] = base ? (char*)base + off : nullptr;
     off += align256(sizes[i]);
   }
@@ -1898,6 +1914,7 @@ static size_t den_ws_layout(const Den* d, int B, int T, void* base, DenWs* w) {
     w->A16 = a16 ? (bf16*)ptrs[9] : nullptr;
     w->XA = xa ? (bf16*)ptrs[10] : nullptr;
     w->XP = (float*)ptrs[11];
+    w->XV = (float*)ptrs[12];
   }
   return off;
 }
@@ -2518,6 +2535,7 @@ static size_t persist_layout(char* base, pk::Params* P) {
   char* xs = take(T * C * 2);
   char* gnp = take((size_t)pk::kGroups * H * 16);
   char* yb = take((size_t)pk::kWGs * 16 * 4);
+  char* xbase = take(T * C * 4);  // two-stage solvers, >= 3 chunks per group: the step's base x (last: the others stay put)
   if (P) {
     P->ctr = reinterpret_cast<int*>(ctr);
     P->sticky = reinterpret_cast<int*>(sticky);
@@ -2531,6 +2549,7 @@ static size_t persist_layout(char* base, pk::Params* P) {
     P->xs = reinterpret_cast<bf16*>(xs);
     P->gnp = reinterpret_cast<float4*>(gnp);
     P->yb = reinterpret_cast<float*>(yb);
+    P->xbase = reinterpret_cast<float*>(xbase);
   }
   return off;
 }
@@ -2603,10 +2622,25 @@ static bool persist_eligible(Den* d, int B, int T) {
   return d->pdev_ok == 1;
 }
 
+// Coefficients of a two-stage second-order solver with stage parameter a in (0, 1] over nsteps uniform steps
+// (flamed_den_solve_rk2): formed in double like the Python floats of the module's own loop, applied in fp32.
+struct Rk2 {
+  double a;
+  float dt, adt, c1, c2dt;
+  Rk2(double a_, int nsteps) : a(a_) {
+    const double h = 1.0 / (double)nsteps;
+    dt = (float)h;
+    adt = (float)(a * h);
+    c1 = (float)((2.0 * a - 1.0) / (2.0 * a * a));
+    c2dt = (float)(1.0 / (2.0 * a) * h);
+  }
+};
+
 // Steps [s0, s1) of a B = 1 solve as ONE cooperative launch, enqueued on `st` with no host synchronisation:
 // the kernel (it resets its own counter block) and, outside a capture, HIP events around it plus an async
 // copy of the sticky failure word.  A failed launch NaN-poisons x and is reported by the next call / persist_info.
-static int persist_solve(Den* d, float* xt, const float* mods, int nfe, int B, int T, int s0, int s1, hipStream_t st) {
+static int persist_solve(Den* d, float* xt, const float* mods, int nfe, int B, int T, int s0, int s1, hipStream_t st,
+                         const Rk2* rk = nullptr) {
   const bool cap = stream_capturing(st);
   FL_REQUIRE(d->pmem && d->pfail_host && d->perr_host, "persistent solve: scratch not allocated at load");
   pk::Params P{};
@@ -2615,6 +2649,9 @@ static int persist_solve(Den* d, float* xt, const float* mods, int nfe, int B, i
   const int Bp = tn().persist_pad ? persist_batch(B) : B;
   P.T = T; P.B = Bp; P.Bx = Bp != B ? B : 0; P.NB = d->NB; P.s0 = s0; P.s1 = s1;
   P.dt = (float)(1.0 / (double)nfe);
+  if (rk) {  // nfe velocity evaluations = nfe / 2 steps
+    P.rk2 = 1; P.dt = rk->dt; P.adt = rk->adt; P.c1 = rk->c1; P.c2dt = rk->c2dt;
+  }
   P.mods = mods; P.MS = d->MS; P.MS0 = d->MS0;
   // the kernel reads modulation rows as 16-B vectors (persist.hip ld_cols)
   FL_REQUIRE(P.MS % 4 == 0 && P.MS0 % 4 == 0 && ((uintptr_t)mods & 15) == 0, "persistent solve: modulation rows not 16-B aligned");
@@ -2662,8 +2699,8 @@ static int persist_solve(Den* d, float* xt, const float* mods, int nfe, int B, i
   return kOk;
 }
 
-static int graph_chunk(int nfe) {
-  const int gs = tn().graph_steps;
+static int graph_chunk(int nfe, int per_step = 1) {
+  const int gs = tn().graph_steps / per_step;  // (per_step launches-worth of Euler steps per solver step)
   for (int g = gs < nfe ? gs : nfe; g > 1; --g)
     if (nfe % g == 0) return g;
   return 1;
@@ -2893,12 +2930,17 @@ static int den_chain_streams(Den* d, int S, hipStream_t st) {
   return kOk;
 }
 
-FLAMED_API int flamed_den_solve_part(flamed_den_t h, float* xt, const float* mods, int nfe, int B, int T, void* ws,
-                                     size_t ws_bytes, int use_graph, int s0, int s1, hipStream_t st) {
+// Velocity evaluations [s0, s1) of an nfe-evaluation solve.  rk null: forward Euler, one evaluation per step.  rk set
+// (flamed_den_solve_rk2; always the whole solve): two evaluations per step, x and the stage state y (the workspace's
+// XP) alternating as the evaluation's input, each evaluation a den_step with a velocity output (XV) followed by
+// rk2_update_kernel; modulation row block k belongs to evaluation k on every path.
+static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe, int B, int T, void* ws, size_t ws_bytes,
+                           int use_graph, int s0, int s1, const Rk2* rk, hipStream_t st) {
   Den* d = reinterpret_cast<Den*>(h);
   FL_REQUIRE(d && d->dev, "flamed_den_solve: handle not loaded");
   FL_REQUIRE(xt && mods && ws && B > 0 && T > 0 && nfe > 0, "flamed_den_solve: bad args");
   FL_REQUIRE(0 <= s0 && s0 < s1 && s1 <= nfe, "flamed_den_solve_part: bad step range [%d, %d) of %d", s0, s1, nfe);
+  FL_REQUIRE(!rk || (nfe % 2 == 0 && s0 == 0 && s1 == nfe), "flamed_den_solve_rk2: whole steps of a whole solve only");
   FL_DEN_CALL(d);
   FL_REQUIRE_ON(xt, d->device, "flamed_den_solve");
   if (ws_bytes < den_solve_ws(d, B, T)) {
@@ -2915,17 +2957,35 @@ FLAMED_API int flamed_den_solve_part(flamed_den_t h, float* xt, const float* mod
     mk = mods + (size_t)k * Bk * d->MS;
     wk = static_cast<char*>(ws) + k * wsk;
   };
+  // evaluation e of a two-stage solve on chain k: v(x) into XV, then y = x + (a dt) v into XP (e even), or v(y)
+  // and the step x += c1 (y - x) + (c2 dt) v in place (e odd)
+  auto rk_eval = [&](int e, int k, const float* mrow, hipStream_t cs, int* ctr) -> int {
+    float* xk; const float* mk; void* wk;
+    sub(k, xk, mk, wk);
+    DenWs wc;
+    den_ws_layout(d, Bk, T, wk, &wc);
+    const bool first = !(e & 1);
+    const int rc = den_step(d, first ? xk : wc.XP, mrow ? mrow : mk, T, Bk, T, 0.f, wc.XV, wk, cs, ctr, nullptr, B, k, S);
+    if (rc) return rc;
+    const size_t nk = (size_t)Bk * T * d->C;
+    hipLaunchKernelGGL(rk2_update_kernel, dim3((nk + 255) / 256), dim3(256), 0, cs, xk, first ? (const float*)nullptr : wc.XP,
+                       wc.XV, first ? wc.XP : xk, nk, first ? 0.f : rk->c1, first ? rk->adt : rk->c2dt);
+    FL_LAUNCH_CHECK();
+    return kOk;
+  };
   if (!(use_graph & 1)) {
     for (int s = s0; s < s1; ++s)
       for (int k = 0; k < S; ++k) {
         float* xk; const float* mk; void* wk;
         sub(k, xk, mk, wk);
-        int rc = den_step(d, xk, mk + s * step_stride, T, Bk, T, dt, nullptr, wk, st, nullptr, nullptr, B, k, S);
+        int rc = rk ? rk_eval(s, k, mk + s * step_stride, st, nullptr)
+                    : den_step(d, xk, mk + s * step_stride, T, Bk, T, dt, nullptr, wk, st, nullptr, nullptr, B, k, S);
         if (rc) return rc;
       }
     return kOk;
   }
-  const int G = graph_chunk(nfe);
+  // a captured chunk of a two-stage solve holds whole steps, so the x / y alternation is baked into the graph
+  const int G = rk ? 2 * graph_chunk(nfe / 2, 2) : graph_chunk(nfe);
   FL_REQUIRE(s0 % G == 0 && (s1 % G == 0 || s1 == nfe), "flamed_den_solve_part: range [%d, %d) not on %d-step graph chunks",
              s0, s1, G);
   // the parts of one solve must run one step structure: a knob change between parts is rejected, and the
@@ -2933,14 +2993,14 @@ FLAMED_API int flamed_den_solve_part(flamed_den_t h, float* xt, const float* mod
   if (s0 == 0) {
     d->part_epoch = d->tune_ver;
     d->ppath = !(use_graph & 2) && persist_eligible(d, B, T) ? 1 : 0;  // bit 2: the caller's retry, no persistent launch
-    d->ppath_key[0] = B; d->ppath_key[1] = T; d->ppath_key[2] = nfe;
+    d->ppath_key[0] = B; d->ppath_key[1] = T; d->ppath_key[2] = rk ? -nfe : nfe;
   }
   FL_REQUIRE(d->part_epoch == d->tune_ver, "flamed_den_solve_part: knobs changed since step 0 of this solve (part [%d, %d))",
              s0, s1);
-  FL_REQUIRE(d->ppath >= 0 && d->ppath_key[0] == B && d->ppath_key[1] == T && d->ppath_key[2] == nfe,
+  FL_REQUIRE(d->ppath >= 0 && d->ppath_key[0] == B && d->ppath_key[1] == T && d->ppath_key[2] == (rk ? -nfe : nfe),
              "flamed_den_solve_part: part [%d, %d) of a solve whose step-0 part did not run on this handle", s0, s1);
   if (d->ppath == 1) {  // one persistent launch for the whole range (B = 1)
-    const int prc = persist_solve(d, xt, mods, nfe, B, T, s0, s1, st);
+    const int prc = persist_solve(d, xt, mods, nfe, B, T, s0, s1, st, rk);
     if (prc == kOk || s0 != 0 || prc != kBadArg) return prc;
     // the runtime refused the cooperative grid (not all 256 workgroups co-resident): this device never
     // runs the persistent solve; this solve (still at step 0) takes the graph of launches
@@ -2950,14 +3010,15 @@ FLAMED_API int flamed_den_solve_part(flamed_den_t h, float* xt, const float* mod
   if (!d->ctr) FL_HIP(hipMalloc(&d->ctr, 256));
   // fused Euler steps: 25 launches per step instead of 26 (the combine rides in the next proj_in); the
   // state ping-pongs between xt (even steps) and the workspace's XP (odd steps), so G must be even
-  const bool fused = S == 1 && den_fused_ok(d, B, T) && G % 2 == 0;
-  const bool fbig = !fused && den_fused_big(d, Bk, T);  // large M: in-place fused steps, per chain
+  // (two-stage solvers take neither fusion: every evaluation writes its velocity)
+  const bool fused = !rk && S == 1 && den_fused_ok(d, B, T) && G % 2 == 0;
+  const bool fbig = !rk && !fused && den_fused_big(d, Bk, T);  // large M: in-place fused steps, per chain
   const bool br = S > 1 && tn().split_graph == 1;
   DenWs w;
   den_ws_layout(d, B, T, ws, &w);
-  // the graph bakes in dt = 1/nfe, so nfe is part of the key
+  // the graph bakes in dt = 1/nfe (and a two-stage solver's coefficients), so nfe and the solver are part of the key
   const bool hit = d->gexec && d->g_B == B && d->g_T == T && d->g_nfe == nfe && d->g_xt == xt && d->g_mods == mods && d->g_ws == ws &&
-                   d->g_epoch == d->tune_ver;
+                   d->g_epoch == d->tune_ver && d->g_a == (rk ? rk->a : 0.0);
   if (!hit) {
     retire_graph(d->gexec);
     for (auto& g : d->gexec_c) retire_graph(g);
@@ -2979,7 +3040,9 @@ FLAMED_API int flamed_den_solve_part(flamed_den_t h, float* xt, const float* mod
         float* xk; const float* mk; void* wk;
         sub(k, xk, mk, wk);
         hipStream_t cs = k == 0 ? d->cap_stream : d->cap_aux[k];
-        for (int s = 0; s < G && rc == kOk; ++s) rc = den_step(d, xk, mk, T, Bk, T, dt, nullptr, wk, cs, d->ctr + 16 * k, fbig ? xk : nullptr, B, k, S);
+        for (int s = 0; s < G && rc == kOk; ++s)
+          rc = rk ? rk_eval(s, k, nullptr, cs, d->ctr + 16 * k)
+                  : den_step(d, xk, mk, T, Bk, T, dt, nullptr, wk, cs, d->ctr + 16 * k, fbig ? xk : nullptr, B, k, S);
       }
       for (int k = 1; k < S && rc == kOk; ++k) {
         FL_HIP(hipEventRecord(d->cap_ev[k], d->cap_aux[k]));
@@ -3000,7 +3063,8 @@ FLAMED_API int flamed_den_solve_part(flamed_den_t h, float* xt, const float* mod
       float* xk; const float* mk; void* wk;
       sub(k, xk, mk, wk);
       for (int s = 0; s < G && rc == kOk; ++s) {
-        if (fused) rc = den_step(d, s % 2 ? w.XP : xt, mods, T, B, T, dt, nullptr, ws, d->cap_stream, d->ctr, s % 2 ? xt : w.XP);
+        if (rk) rc = rk_eval(s, k, nullptr, d->cap_stream, d->ctr + 16 * k);
+        else if (fused) rc = den_step(d, s % 2 ? w.XP : xt, mods, T, B, T, dt, nullptr, ws, d->cap_stream, d->ctr, s % 2 ? xt : w.XP);
         else rc = den_step(d, xk, mk, T, Bk, T, dt, nullptr, wk, d->cap_stream, d->ctr + 16 * k, fbig ? xk : nullptr, B, k, S);
       }
       hipGraph_t g = nullptr;
@@ -3013,6 +3077,7 @@ FLAMED_API int flamed_den_solve_part(flamed_den_t h, float* xt, const float* mod
       FL_HIP(ie);
     }
     d->g_B = B; d->g_T = T; d->g_nfe = nfe; d->g_epoch = d->tune_ver; d->g_xt = xt; d->g_mods = mods; d->g_ws = ws;
+    d->g_a = rk ? rk->a : 0.0;
   }
   const size_t n = (size_t)B * T * d->C;
   if (s0 == 0) {
@@ -3078,6 +3143,21 @@ FLAMED_API int flamed_den_solve_part(flamed_den_t h, float* xt, const float* mod
     }
   }
   return kOk;
+}
+
+FLAMED_API int flamed_den_solve_part(flamed_den_t h, float* xt, const float* mods, int nfe, int B, int T, void* ws,
+                                     size_t ws_bytes, int use_graph, int s0, int s1, hipStream_t st) {
+  return den_solve_range(h, xt, mods, nfe, B, T, ws, ws_bytes, use_graph, s0, s1, nullptr, st);
+}
+
+FLAMED_API int flamed_den_solve_rk2(flamed_den_t h, float* xt, const float* mods, int nsteps, double a, int B, int T,
+                                    void* ws, size_t ws_bytes, int use_graph, hipStream_t st) {
+  // host-side argument checks, before anything touches the handle or a device
+  FL_REQUIRE(nsteps >= 1 && nsteps <= (1 << 29), "flamed_den_solve_rk2: nsteps = %d (at least 1)", nsteps);
+  FL_REQUIRE(a > 0.0 && a <= 1.0, "flamed_den_solve_rk2: stage parameter a = %g outside (0, 1]", a);
+  FL_REQUIRE(h && xt && mods && ws, "flamed_den_solve_rk2: null handle, state, modulation table or workspace");
+  const Rk2 rk(a, nsteps);
+  return den_solve_range(h, xt, mods, 2 * nsteps, B, T, ws, ws_bytes, use_graph, 0, 2 * nsteps, &rk, st);
 }
 
 }  // extern "C"

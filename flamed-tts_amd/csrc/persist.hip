@@ -771,7 +771,10 @@ __device__ __forceinline__ float2 gn_finalize(const float (&nv)[kGroups], const 
 // KH: GEMM phases split 2 x 2 over the waves (gemm_kh, persist_opt 1024): a template parameter, so each variant
 // gets its own register allocation
 // NTW: chunks of 64 rows per group (template: registers are indexed by it), 1..kMaxNTW; KH only with NTW == 1.
-template <bool KH, int NTW>
+// RK2: the two-stage second-order update (Params::rk2) with a base copy of the state, in registers up to two chunks
+// and in a thread-private global stash beyond (kStash below); the Euler variants (RK2 = false) compile exactly the
+// code they had before it existed.
+template <bool KH, int NTW, bool RK2 = false>
 __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -877,6 +880,20 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
     if (row < nr && !idle) {
       xs0[i] = P.xt[(size_t)(r0 + row) * kC + xch];
       xs1[i] = P.xt[(size_t)(r0 + row) * kC + xch + 1];
+    }
+  }
+  // RK2: xs is the state the next evaluation reads (x on a step's first evaluation, the stage state y on its
+  // second); xb keeps the step's base x.  Each thread owns its rows for the whole solve: no hand-off.
+  // From three chunks per group on the Euler variants are already out of registers (they spill), so there the base
+  // lives in a thread-private global stash instead (P.xbase, this thread's own elements: written at the first
+  // evaluation, when it still equals xs, read back at the second) and costs no register across the phases.
+  constexpr bool kStash = RK2 && NTW >= 3;
+  [[maybe_unused]] float xb0[RK2 && !kStash ? NTW : 1], xb1[RK2 && !kStash ? NTW : 1];
+  if constexpr (RK2 && !kStash) {
+#pragma unroll
+    for (int i = 0; i < NTW; ++i) {
+      xb0[i] = xs0[i];
+      xb1[i] = xs1[i];
     }
   }
   // An abandoned solve leaves NaN in this workgroup's part of x (every workgroup leaves through here or
@@ -1618,8 +1635,32 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
           }
           vv[e] = v;
         }
-        xs0[ci] = __fadd_rn(xs0[ci], __fmul_rn(P.dt, vv[0]));
-        xs1[ci] = __fadd_rn(xs1[ci], __fmul_rn(P.dt, vv[1]));
+        if constexpr (RK2) {
+          // (row < nr: r0 + row < B T <= kMaxT, the stash's rows)
+          float2* const stash = reinterpret_cast<float2*>(P.xbase + (size_t)t * kC + xch);
+          if (!(step & 1)) {  // first evaluation of the step: the stage state y (published below as proj_in's operand)
+            if constexpr (kStash) *stash = make_float2(xs0[ci], xs1[ci]);  // xs still holds the base x here
+            xs0[ci] = __fadd_rn(xs0[ci], __fmul_rn(P.adt, vv[0]));
+            xs1[ci] = __fadd_rn(xs1[ci], __fmul_rn(P.adt, vv[1]));
+          } else {  // second: x + c1 (y - x) + c2 dt v(y), where c1 (y - x) = c1 a dt v(x)
+            float b0, b1;
+            if constexpr (kStash) {
+              const float2 b = *stash;
+              b0 = b.x; b1 = b.y;
+            } else {
+              b0 = xb0[ci]; b1 = xb1[ci];
+            }
+            xs0[ci] = __fadd_rn(__fadd_rn(b0, __fmul_rn(P.c1, __fsub_rn(xs0[ci], b0))), __fmul_rn(P.c2dt, vv[0]));
+            xs1[ci] = __fadd_rn(__fadd_rn(b1, __fmul_rn(P.c1, __fsub_rn(xs1[ci], b1))), __fmul_rn(P.c2dt, vv[1]));
+            if constexpr (!kStash) {
+              xb0[ci] = xs0[ci];
+              xb1[ci] = xs1[ci];
+            }
+          }
+        } else {
+          xs0[ci] = __fadd_rn(xs0[ci], __fmul_rn(P.dt, vv[0]));
+          xs1[ci] = __fadd_rn(xs1[ci], __fmul_rn(P.dt, vv[1]));
+        }
       }
     }
     __syncthreads();  // yl (staging) is rewritten by publish_xs
@@ -1660,23 +1701,27 @@ int persist_stamps(void* buf, int step) {
 }
 #endif
 
-// Every kernel variant: [0] the 2 x 2 wave-split GEMM (persist_opt 1024, one chunk), [ntw] ntw chunks per group.
-static const void* const* persist_kernels() {
-  static const void* const k[kMaxNTW + 1] = {
-      reinterpret_cast<const void*>(den_persist_kernel<true, 1>), reinterpret_cast<const void*>(den_persist_kernel<false, 1>),
-      reinterpret_cast<const void*>(den_persist_kernel<false, 2>), reinterpret_cast<const void*>(den_persist_kernel<false, 3>),
-      reinterpret_cast<const void*>(den_persist_kernel<false, 4>), reinterpret_cast<const void*>(den_persist_kernel<false, 5>),
-      reinterpret_cast<const void*>(den_persist_kernel<false, 6>), reinterpret_cast<const void*>(den_persist_kernel<false, 7>),
-      reinterpret_cast<const void*>(den_persist_kernel<false, 8>)};
+// Every kernel variant: [0] the 2 x 2 wave-split GEMM (persist_opt 1024, one chunk), [ntw] ntw chunks per group;
+// the RK2 variants follow in the same order.
+constexpr int kVariants = kMaxNTW + 1;
+template <bool RK2>
+static const void* persist_kernel_of(int i) {
+  static const void* const k[kVariants] = {
+      reinterpret_cast<const void*>(den_persist_kernel<true, 1, RK2>), reinterpret_cast<const void*>(den_persist_kernel<false, 1, RK2>),
+      reinterpret_cast<const void*>(den_persist_kernel<false, 2, RK2>), reinterpret_cast<const void*>(den_persist_kernel<false, 3, RK2>),
+      reinterpret_cast<const void*>(den_persist_kernel<false, 4, RK2>), reinterpret_cast<const void*>(den_persist_kernel<false, 5, RK2>),
+      reinterpret_cast<const void*>(den_persist_kernel<false, 6, RK2>), reinterpret_cast<const void*>(den_persist_kernel<false, 7, RK2>),
+      reinterpret_cast<const void*>(den_persist_kernel<false, 8, RK2>)};
   static_assert(kMaxNTW == 8, "kernel table");
-  return k;
+  return k[i];
 }
+static const void* persist_kernel(int i, bool rk2) { return rk2 ? persist_kernel_of<true>(i) : persist_kernel_of<false>(i); }
 
 bool persist_device_ok(int device) {
   int cus = 0, nb = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus != kWGs) return false;
-  for (int i = 0; i <= kMaxNTW; ++i) {
-    const void* k = persist_kernels()[i];
+  for (int i = 0; i < 2 * kVariants; ++i) {
+    const void* k = persist_kernel(i % kVariants, i >= kVariants);
     if (set_max_lds(k) != hipSuccess) return false;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kThreads, kLds) != hipSuccess || nb < 1) return false;
   }
@@ -1699,7 +1744,11 @@ int persist_launch(const Params& Pin, hipStream_t st, bool cooperative) {
     set_error("persistent solve: %d row chunks per group (1..%d; the wave-split GEMM variant takes one)", P.ntw, kMaxNTW);
     return kBadArg;
   }
-  const void* kern = persist_kernels()[(P.opt & 1024) ? 0 : P.ntw];
+  if (P.rk2 && ((P.s0 & 1) || (P.s1 & 1))) {
+    set_error("persistent solve: a two-stage solver runs whole steps (evaluations [%d, %d))", P.s0, P.s1);
+    return kBadArg;
+  }
+  const void* kern = persist_kernel((P.opt & 1024) ? 0 : P.ntw, P.rk2 != 0);
   // tune coop 0: plain launch (profiling: rocprofv3's teardown faults after cooperative launches, README);
   // residency was checked by persist_eligible either way
   const hipError_t e = cooperative && tn().coop ? hipLaunchCooperativeKernel(kern, dim3(kWGs), dim3(kThreads), args, kLds, st)

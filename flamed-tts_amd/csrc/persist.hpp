@@ -122,6 +122,13 @@ struct Params {
   int pst_step = -1;
   float* gnd = nullptr;               // FL_STAMPS builds: GroupNorm exchange dump of step gnd_step (rowpart_probe.py)
   int gnd_step = -1;
+  // two-stage second-order solver (the RK2 kernel variants; the Euler variants never read these): [s0, s1) then
+  // counts velocity evaluations, two per step with s0 even, evaluation k reads modulation row block k;
+  //   even k: y = x + adt v(x)        odd k: x = x + c1 (y - x) + c2dt v(y)
+  int rk2 = 0;
+  float adt = 0.f, c1 = 0.f, c2dt = 0.f;
+  float* xbase = nullptr;  // the step's base x of the variants with >= 3 chunks per group (B T x C, thread-private
+                           // elements: each thread stores and reloads its own)
 };
 
 // Host side (persist.hip): whether this device runs the 256-workgroup grid fully resident, and the launch.

@@ -71,8 +71,11 @@ class Flamed(nn.Module):
     def sample(self, text: str = None, phonemes: torch.Tensor = None, prompt_raw=None, prompt_processed=None,
                timbre: torch.Tensor = None, sr: int = 16000, codec_cfg=None, codec_encoder=None, codec_decoder=None,
                temp_durgen: float = 0.3, temp_denoiser: float = 0.3, nsteps_durgen: int = 64,
-               nsteps_denoiser: int = 64, lexicon_path: str = None, cleaners=("english_cleaners",)):
-        """reference :89-166 (same argument validation and ValueErrors)."""
+               nsteps_denoiser: int = 64, lexicon_path: str = None, cleaners=("english_cleaners",),
+               solver_denoiser: str = "euler"):
+        """reference :89-166 (same argument validation and ValueErrors).  solver_denoiser: the denoiser's ODE
+        solver ("euler", the reference's; "midpoint" / "heun": second order, nsteps_denoiser then counts velocity
+        evaluations and must be even -- ProbGenerator.sample)."""
         if codec_decoder is None or (codec_encoder is None and prompt_raw is not None):
             if codec_cfg is None:
                 raise ValueError("The codec_encoder or codec_decoder is set to None. To initialize the codec encoder or "
@@ -108,14 +111,15 @@ class Flamed(nn.Module):
                                                     device=self.device),
                                 prompts=prompts, timbres=timbre, codec_decoder=codec_decoder, temp_durgen=temp_durgen,
                                 temp_denoiser=temp_denoiser, nsteps_durgen=nsteps_durgen,
-                                nsteps_denoiser=nsteps_denoiser)
+                                nsteps_denoiser=nsteps_denoiser, solver_denoiser=solver_denoiser)
         wav = out["wav"][0][0].detach().cpu().numpy()
         return {"wav": wav, "time": time.time() - start}
 
     @torch.inference_mode()
     def sample_batch(self, phonemes, src_lens, prompts, timbres, codec_decoder=None, temp_durgen: float = 0.3,
-                     temp_denoiser: float = 0.3, nsteps_durgen: int = 64, nsteps_denoiser: int = 64):
-        """reference :168-217"""
+                     temp_denoiser: float = 0.3, nsteps_durgen: int = 64, nsteps_denoiser: int = 64,
+                     solver_denoiser: str = "euler"):
+        """reference :168-217; solver_denoiser as in sample"""
         start = time.time()
         dev = self.device
         phonemes, src_lens, prompts, timbres = phonemes.to(dev), src_lens.to(dev), prompts.to(dev), timbres.to(dev)
@@ -123,7 +127,8 @@ class Flamed(nn.Module):
             texts=phonemes, src_lens=src_lens, max_src_len=phonemes.size(-1), prompts=prompts,
             prompts_len=prompts.size(-1), nfe=nsteps_durgen, temperature=temp_durgen)
         latents = self.prob_generator.sample(cond=prior_emb_cond, spk=timbres, nfe=nsteps_denoiser,
-                                             temperature=temp_denoiser, mask=~tgt_mask.unsqueeze(-1))
+                                             temperature=temp_denoiser, mask=~tgt_mask.unsqueeze(-1),
+                                             solver=solver_denoiser)
         if latents.is_cuda:
             torch.cuda.synchronize(latents.device)  # 'time' covers the device work, as the eager reference does
             den = self.prob_generator.denoiser

@@ -30,6 +30,11 @@ from flamed import ops
 from flamed.utils.conv import GemmConv1d
 
 
+# ODE solvers of ProbGenerator.sample: name -> stage parameter a of the two-stage second-order family
+# (None: the reference's forward Euler loop)
+SOLVERS = {"euler": None, "midpoint": 0.5, "heun": 1.0}
+
+
 def modulate(x, shift, scale):
     """reference :7-8"""
     return x * (1 + scale) + shift
@@ -326,19 +331,45 @@ class ProbGenerator(nn.Module):
         x1_est = (xt + (1 - k * t) * vt) * mask
         return {"fm_loss": F.mse_loss(vt, dx), "anchor_loss": F.mse_loss(x1_est, x1)}
 
-    def sample(self, cond, spk, mask, nfe=4, temperature=1.0):
+    def sample(self, cond, spk, mask, nfe=4, temperature=1.0, solver="euler"):
         """reference :434-447.  Noise is drawn from the global CPU RNG with the reference's shape and
-        order, so seeded runs reproduce the reference trajectory."""
+        order, so seeded runs reproduce the reference trajectory.
+
+        solver: "euler" (the reference's loop, the default), or a two-stage second-order method, "midpoint"
+        (a = 1/2) or "heun" (a = 1).  nfe always counts velocity evaluations, so a second-order solver takes
+        nfe / 2 steps of dt = 2 / nfe (nfe even):
+            y      = x + (a dt) v(x, t_i)
+            x_next = x + c1 (y - x) + (c2 dt) v(y, t_i + a dt),  c1 = (2a - 1) / (2 a^2),  c2 = 1 / (2a)"""
+        if solver not in SOLVERS:
+            raise ValueError(f"unknown solver {solver!r}; use one of {sorted(SOLVERS)}")
+        a = SOLVERS[solver]
+        if a is not None and (nfe < 2 or nfe % 2):
+            raise ValueError(f"solver {solver!r} takes two velocity evaluations per step: nfe must be even, got {nfe}")
         cond = self.fold_condition(cond, mask)
         b, l, _ = cond.shape
-        ts = torch.linspace(0, 1, nfe + 1, device=cond.device)
         xt = torch.randn((b, l, self.target_dim)).to(cond.device) * temperature + cond
+        if a is None:
+            ts = torch.linspace(0, 1, nfe + 1, device=cond.device)
+            if self.denoiser._use_hip(xt):
+                xt = ops.den_solve(self.denoiser.hip().oid, xt, ts, spk, nfe)
+            else:
+                delta_t = 1 / nfe
+                for i in range(1, len(ts)):
+                    xt = xt + delta_t * self.denoiser(xt, ts[i - 1].unsqueeze(0).unsqueeze(1), spk)
+            return xt.transpose(1, -1)
+        nsteps = nfe // 2
+        ts = torch.linspace(0, 1, nsteps + 1, device=cond.device)
+        delta_t = 1 / nsteps
+        c1, c2 = (2 * a - 1) / (2 * a * a), 1 / (2 * a)
         if self.denoiser._use_hip(xt):
-            xt = ops.den_solve(self.denoiser.hip().oid, xt, ts, spk, nfe)
+            # evaluation times [t_0, t_0 + a dt, t_1, t_1 + a dt, ...]: one modulation row block per evaluation
+            ts_eval = torch.stack((ts[:-1], ts[:-1] + a * delta_t), dim=1).reshape(-1)
+            xt = ops.den_solve_rk2(self.denoiser.hip().oid, xt, ts_eval, spk, nsteps, a)
         else:
-            delta_t = 1 / nfe
-            for i in range(1, len(ts)):
-                xt = xt + delta_t * self.denoiser(xt, ts[i - 1].unsqueeze(0).unsqueeze(1), spk)
+            for i in range(nsteps):
+                y = xt + (a * delta_t) * self.denoiser(xt, ts[i].unsqueeze(0).unsqueeze(1), spk)
+                v = self.denoiser(y, (ts[i] + a * delta_t).unsqueeze(0).unsqueeze(1), spk)
+                xt = (xt + c1 * (y - xt) if c1 else xt) + (c2 * delta_t) * v
         return xt.transpose(1, -1)
 
 
@@ -381,7 +412,9 @@ class DenoiserHIP:
         # on the graph of launches into the same output tensor, so a failure never survives to the caller's
         # host copy; skipped inside a stream capture (the caller then owns the check: persist_status)
         self.check_persist = True
-        self._pending = []  # (launch seq, output, input x, ts, spk, nfe) of solves not yet known to have succeeded
+        # (launch seq, output, input x, ts, spk, nfe, a) of solves not yet known to have succeeded (a: the stage
+        # parameter of a two-stage solve, None for Euler; nfe counts velocity evaluations either way)
+        self._pending = []
         self.oid = ops.register(self)  # torch.ops.flamed_hip.den_* carry this id
 
     def __del__(self):
@@ -500,6 +533,20 @@ class DenoiserHIP:
     def solve(self, xt: torch.Tensor, ts: torch.Tensor, spk: torch.Tensor, nfe: int) -> torch.Tensor:
         """Full Euler solve; returns a new (B,T,C) fp32 tensor.  Only enqueues work: a persistent launch is
         checked later (settle), and a failed one re-written in place before the caller's next sync point."""
+        return self._solve(xt, ts, spk, nfe, None)
+
+    def solve_rk2(self, xt: torch.Tensor, ts_eval: torch.Tensor, spk: torch.Tensor, nsteps: int, a: float) -> torch.Tensor:
+        """Full solve with the two-stage second-order method of stage parameter a (0.5 midpoint, 1 Heun):
+        nsteps steps, ts_eval the 2 nsteps evaluation times [t_0, t_0 + a dt, t_1, t_1 + a dt, ...]
+        (flamed_den_solve_rk2).  Same contract as solve, and a failed persistent launch is re-run as RK2."""
+        nsteps, a = int(nsteps), float(a)
+        if nsteps < 1 or not 0.0 < a <= 1.0:
+            raise ValueError(f"solve_rk2: nsteps >= 1 and 0 < a <= 1 required; got nsteps = {nsteps}, a = {a}")
+        if ts_eval.numel() < 2 * nsteps:
+            raise ValueError(f"solve_rk2: {2 * nsteps} evaluation times required, got {ts_eval.numel()}")
+        return self._solve(xt, ts_eval, spk, 2 * nsteps, a)
+
+    def _solve(self, xt, ts, spk, nfe, a):
         dev = xt.device
         self._ensure(dev)
         B, T, C = xt.shape
@@ -508,12 +555,12 @@ class DenoiserHIP:
         if self._pending and not capturing:  # (event queries are not allowed while a stream captures)
             self.settle(block=False)
         runs0, _ = self.persist_status()
-        x = self._launch(xt, ts, spk, nfe, 0)
+        x = self._launch(xt, ts, spk, nfe, 0, a)
         out = x.clone()
         if self.check_persist and not capturing and self.persist_status()[0] > runs0:
             seq = ctypes.c_longlong(-1)
             nat.check(nat.lib().flamed_den_persist_last(self.handle, ctypes.byref(seq)), "flamed_den_persist_last")
-            self._pending.append((seq.value, out, xt.detach().clone(), ts.detach().clone(), spk.detach().clone(), nfe))
+            self._pending.append((seq.value, out, xt.detach().clone(), ts.detach().clone(), spk.detach().clone(), nfe, a))
             if len(self._pending) > 32:  # the launch ring holds 64: settle the oldest before their slots are reused
                 self.settle(block=True)
         return out
@@ -531,7 +578,7 @@ class DenoiserHIP:
             torch.cuda.synchronize(self._pending[0][1].device)
         keep, reruns = [], 0
         for rec in self._pending:
-            seq, out, x0, ts, spk, nfe = rec
+            seq, out, x0, ts, spk, nfe, a = rec
             st = ctypes.c_int(0)
             nat.check(L.flamed_den_persist_query(self.handle, seq, ctypes.byref(st)), "flamed_den_persist_query")
             state = st.value
@@ -543,17 +590,18 @@ class DenoiserHIP:
             if state == 1:
                 warnings.warn("flamed: persistent solve failed (its output was NaN-poisoned); "
                               "re-running it on the graph of launches")
-                out.copy_(self._launch(x0, ts, spk, nfe, 2))
+                out.copy_(self._launch(x0, ts, spk, nfe, 2, a))  # with the solver of the failed launch
                 reruns += 1
         self._pending = keep
         return reruns
 
-    def _launch(self, xt, ts, spk, nfe, extra_graph_bits):
-        """AdaLN rows + flamed_den_solve into the handle's solve buffer (returned, not copied)."""
+    def _launch(self, xt, ts, spk, nfe, extra_graph_bits, a=None):
+        """AdaLN rows + flamed_den_solve (a None) or flamed_den_solve_rk2 (stage parameter a) into the handle's
+        solve buffer (returned, not copied); nfe velocity evaluations at the times ts[:nfe]."""
         dev = xt.device
         B, T, C = xt.shape
         L = nat.lib()
-        key = (B, T, nfe)
+        key = (B, T, nfe) if a is None else (B, T, nfe, a)
         bufs = self._solve_bufs.get(key)
         if bufs is None:
             r = torch.arange(nfe * B, device=dev)
@@ -568,6 +616,11 @@ class DenoiserHIP:
         self.adaln(ts[:nfe], spk, bufs["tidx"], bufs["sidx"], out=bufs["mods"])
         bufs["x"].copy_(xt)
         use_graph = int(bool(self.den.hip_graph)) | extra_graph_bits
+        if a is not None:
+            nat.check(L.flamed_den_solve_rk2(self.handle, nat.ptr(bufs["x"]), nat.ptr(bufs["mods"]), nfe // 2, a, B, T,
+                                             nat.ptr(ws), ws.numel(), use_graph, nat.stream_ptr(dev)),
+                      "flamed_den_solve_rk2" if not extra_graph_bits else "flamed_den_solve_rk2 (re-run)")
+            return bufs["x"]
         nat.check(L.flamed_den_solve(self.handle, nat.ptr(bufs["x"]), nat.ptr(bufs["mods"]), nfe, B, T, nat.ptr(ws),
                                      ws.numel(), use_graph, nat.stream_ptr(dev)),
                   "flamed_den_solve" if not extra_graph_bits else "flamed_den_solve (re-run)")

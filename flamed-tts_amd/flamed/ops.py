@@ -11,6 +11,7 @@ take tensors and scalars only); the registry holds weak references, so a dropped
   op                                    reference function it stands for
   flamed_hip::den_velocity(id, x, t, c)            SimpleMLPAdaLN.forward          prob_generator.py:349-365
   flamed_hip::den_solve(id, xt, ts, spk, nfe)      ProbGenerator.sample Euler loop prob_generator.py:439-445
+  flamed_hip::den_solve_rk2(id, xt, ts_eval, spk, nsteps, a)  the same loop, two-stage second-order solver
   flamed_hip::cond_fold(id, cond, mask)            QuantizerEncoding + ConditionDownSampler :167-205, 435-436
   flamed_hip::pva_flow(id, x, mask, dur, sil, ts, nfe)  PVA.sample Euler loops       pva.py:97-109
   flamed_hip::length_regulate(x, pd, sd, lens, max_len, log_domain)  LengthRegulator.LR  pva.py:125-166
@@ -73,6 +74,16 @@ def den_solve(oid: int, xt: Tensor, ts: Tensor, spk: Tensor, nfe: int) -> Tensor
 
 @den_solve.register_fake
 def _(oid, xt, ts, spk, nfe):
+    return xt.new_empty(xt.shape, dtype=torch.float32)
+
+
+@torch.library.custom_op("flamed_hip::den_solve_rk2", mutates_args=())
+def den_solve_rk2(oid: int, xt: Tensor, ts_eval: Tensor, spk: Tensor, nsteps: int, a: float) -> Tensor:
+    return owner(oid).solve_rk2(xt, ts_eval, spk, nsteps, a)
+
+
+@den_solve_rk2.register_fake
+def _(oid, xt, ts_eval, spk, nsteps, a):
     return xt.new_empty(xt.shape, dtype=torch.float32)
 
 
@@ -180,5 +191,5 @@ def _(oid, x, tgt_mask, prompts, prompts_len):
     return x.new_empty((B, nq, T, D)), x.new_empty((B, V1, nq, T))
 
 
-OPS = ("den_velocity", "den_solve", "cond_fold", "pva_flow", "length_regulate", "fac_decode", "enc_encode",
+OPS = ("den_velocity", "den_solve", "den_solve_rk2", "cond_fold", "pva_flow", "length_regulate", "fac_decode", "enc_encode",
        "vq_encode", "prior_encode", "prior_decode")

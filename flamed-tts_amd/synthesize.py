@@ -192,10 +192,16 @@ class RtfMeter:
         return sum(d * SR / HOP for d in self.durations) / total if total > 0 else float("nan")
 
 
+def _solver_suffix(solver_denoiser: str) -> str:
+    return "" if solver_denoiser == "euler" else f"-{solver_denoiser}"
+
+
 def synthesize_with_prompts(model: Flamed, codec_encoder, codec_decoder, text: str, prompt_dir: str,
                             prompt_list: List[str], output_dir: str, nsteps_durgen: int, nsteps_denoiser: int,
-                            temp_durgen: float, temp_denoiser: float, meter: Optional[RtfMeter] = None):
-    """One `Flamed.sample` per prompt (reference :194-217)."""
+                            temp_durgen: float, temp_denoiser: float, meter: Optional[RtfMeter] = None,
+                            solver_denoiser: str = "euler"):
+    """One `Flamed.sample` per prompt (reference :194-217).  A denoiser solver other than Euler is appended to the
+    output names, so runs with different solvers do not overwrite each other."""
     os.makedirs(output_dir, exist_ok=True)
     meter = meter if meter is not None else RtfMeter()
     rank, world, _ = fdist.dist_env()
@@ -203,10 +209,10 @@ def synthesize_with_prompts(model: Flamed, codec_encoder, codec_decoder, text: s
         audio_prompt = load_audio(_resolve_prompt_path(prompt_dir, prompt_name))
         res = model.sample(text=text, prompt_raw=audio_prompt, sr=SR, codec_encoder=codec_encoder,
                            codec_decoder=codec_decoder, nsteps_durgen=nsteps_durgen, nsteps_denoiser=nsteps_denoiser,
-                           temp_durgen=temp_durgen, temp_denoiser=temp_denoiser)
+                           temp_durgen=temp_durgen, temp_denoiser=temp_denoiser, solver_denoiser=solver_denoiser)
         meter.add(res["time"], len(res["wav"]))
         stem = os.path.splitext(os.path.basename(prompt_name))[0]
-        out_name = f"{stem}-{nsteps_durgen}-{nsteps_denoiser}-{temp_durgen}-{temp_denoiser}.wav"
+        out_name = f"{stem}-{nsteps_durgen}-{nsteps_denoiser}-{temp_durgen}-{temp_denoiser}{_solver_suffix(solver_denoiser)}.wav"
         write_wav(os.path.join(output_dir, out_name), res["wav"], SR)
     return meter.rtf()
 
@@ -214,11 +220,12 @@ def synthesize_with_prompts(model: Flamed, codec_encoder, codec_decoder, text: s
 def synthesize_with_metadata(model: Flamed, codec_encoder, codec_decoder, metadata_file: str, prompt_dir: str,
                              output_dir: str, nsteps_durgen: int, nsteps_denoiser: int, temp_durgen: float,
                              temp_denoiser: float, skip_existing: bool, batch_size: int,
-                             meter: Optional[RtfMeter] = None):
-    """Batched `Flamed.sample_batch` over a `target|prompt|text` file (reference :220-303)."""
+                             meter: Optional[RtfMeter] = None, solver_denoiser: str = "euler"):
+    """Batched `Flamed.sample_batch` over a `target|prompt|text` file (reference :220-303).  A denoiser solver
+    other than Euler is appended to the target directory's name."""
     with open(metadata_file, "r", encoding="utf-8") as fin:
         entries = [line.strip() for line in fin if line.strip()]
-    target_dir = os.path.join(output_dir, f"nfe{nsteps_denoiser}-temp{temp_denoiser}")
+    target_dir = os.path.join(output_dir, f"nfe{nsteps_denoiser}-temp{temp_denoiser}{_solver_suffix(solver_denoiser)}")
     os.makedirs(target_dir, exist_ok=True)
     meter = meter if meter is not None else RtfMeter()
     cache: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
@@ -245,7 +252,8 @@ def synthesize_with_metadata(model: Flamed, codec_encoder, codec_decoder, metada
         phonemes, src_lens, prompts, timbres = build_metadata_batch(model, codec_encoder, codec_decoder, batch, cache)
         out = model.sample_batch(phonemes=phonemes, src_lens=src_lens, prompts=prompts, timbres=timbres,
                                  codec_decoder=codec_decoder, temp_durgen=temp_durgen, temp_denoiser=temp_denoiser,
-                                 nsteps_durgen=nsteps_durgen, nsteps_denoiser=nsteps_denoiser)
+                                 nsteps_durgen=nsteps_durgen, nsteps_denoiser=nsteps_denoiser,
+                                 solver_denoiser=solver_denoiser)
         per_sample = out["time"] / len(batch)
         for item, wav_t in zip(batch, out["wav"]):
             wav = wav_t[0].detach().cpu().numpy()
@@ -292,6 +300,9 @@ def build_arg_parser():
     p.add_argument("--weights-only", type=str2bool, default=True, help="Load checkpoint weights_only flag (default: True).")
     p.add_argument("--nsteps-durgen", type=int, default=64, help="Duration generator sampling steps.")
     p.add_argument("--nsteps-denoiser", type=int, default=64, help="Denoiser sampling steps.")
+    p.add_argument("--solver-denoiser", type=str, default="euler", choices=["euler", "midpoint", "heun"],
+                   help="Denoiser ODE solver; midpoint / heun are second order and --nsteps-denoiser (even) then "
+                        "counts velocity evaluations.")
     p.add_argument("--temp-durgen", type=float, default=0.3, help="Duration generator temperature.")
     p.add_argument("--temp-denoiser", type=float, default=0.3, help="Denoiser temperature.")
     p.add_argument("--device", type=str, default="cuda:0", help="Device to run inference on.")
@@ -326,7 +337,8 @@ def main(args: Optional[argparse.Namespace] = None):
     meter = RtfMeter()
     common = dict(model=model, codec_encoder=codec_encoder, codec_decoder=codec_decoder, prompt_dir=args.prompt_dir,
                   output_dir=args.output_dir, nsteps_durgen=args.nsteps_durgen, nsteps_denoiser=args.nsteps_denoiser,
-                  temp_durgen=args.temp_durgen, temp_denoiser=args.temp_denoiser, meter=meter)
+                  temp_durgen=args.temp_durgen, temp_denoiser=args.temp_denoiser, meter=meter,
+                  solver_denoiser=getattr(args, "solver_denoiser", "euler"))
     if args.metadata_file:
         rtf = synthesize_with_metadata(metadata_file=args.metadata_file, skip_existing=args.skip_existing,
                                        batch_size=args.batch_size, **common)

@@ -108,6 +108,17 @@ FLAMED_API int flamed_den_solve_chunk(flamed_den_t h, int nfe);
  * stream-ordered and use the same arguments apart from s0 / s1. */
 FLAMED_API int flamed_den_solve_part(flamed_den_t h, float* xt, const float* mods, int nfe, int B, int T, void* ws,
                                      size_t ws_bytes, int use_graph, int s0, int s1, hipStream_t stream);
+/* The same solve with a two-stage second-order method of stage parameter a in (0, 1] (1/2: midpoint, 1: Heun,
+ * 2/3: Ralston), nsteps uniform steps of dt = 1 / nsteps, two velocity evaluations each:
+ *     y      = x + (a dt) v(x, t_i)
+ *     x_next = x + c1 (y - x) + (c2 dt) v(y, t_i + a dt),   c1 = (2a - 1) / (2 a^2),  c2 = 1 / (2a)
+ * (coefficients formed in double, applied in fp32).  mods holds 2*nsteps*B rows in evaluation-major order, for
+ * the times [t_0, t_0 + a dt, t_1, t_1 + a dt, ...] (flamed_den_adaln takes arbitrary times).  use_graph has
+ * the bits of flamed_den_solve, and the persistent solve below is taken under the same conditions with the same
+ * failure semantics (NaN poison, counted, flamed_den_persist_status / _query).  nsteps < 1, a outside (0, 1]
+ * or a null pointer return 1001 with a flamed_last_error text.  There is no _part / _chunk form. */
+FLAMED_API int flamed_den_solve_rk2(flamed_den_t h, float* xt, const float* mods, int nsteps, double a, int B, int T,
+                                    void* ws, size_t ws_bytes, int use_graph, hipStream_t stream);
 /* The persistent solve (one launch of 256 workgroups for every step, flamed_tune "persist"; taken by
  * flamed_den_solve / _solve_part with use_graph != 0 on a bf16 handle for one utterance of 16..4096 frames,
  * or -- "persist_multi", default on -- for B = 2 / 4 / 8 equal-length utterances with B x T <= 4096 (and, knob
