@@ -653,11 +653,15 @@ struct Enc {
 
 static int kpad64(int k) { return (k + 63) / 64 * 64; }
 
+// Conv1d(k = 2s, stride s, pad ceil(s/2)) output length: floor((n + 2p - 2s) / s) + 1, and 0 where the kernel
+// does not fit the padded input (int division truncates toward zero: the plain formula gives 1 there).
+static int enc_stride_len(int n, int s) {
+  const int p = s / 2 + s % 2, span = n + 2 * p - 2 * s;
+  return span < 0 ? 0 : span / s + 1;
+}
+
 static int enc_len_after(const Enc* e, int n, int upto) {  // sequence length after `upto` blocks
-  for (int i = 0; i < upto; ++i) {
-    const int s = e->ratios[i], p = s / 2 + s % 2;
-    n = (n + 2 * p - 2 * s) / s + 1;
-  }
+  for (int i = 0; i < upto; ++i) n = enc_stride_len(n, e->ratios[i]);
   return n;
 }
 
@@ -668,8 +672,7 @@ static size_t enc_ws_layout(const Enc* e, int B, int n, void* base, EncWs* w) {
   int len = n, d = e->ngf;
   for (int i = 0; i < e->NDN; ++i) {
     maxcn = maxcn > (size_t)len * d ? maxcn : (size_t)len * d;
-    const int s = e->ratios[i], p = s / 2 + s % 2;
-    len = (len + 2 * p - 2 * s) / s + 1;
+    len = enc_stride_len(len, e->ratios[i]);
     d *= 2;
     maxcn = maxcn > (size_t)len * d ? maxcn : (size_t)len * d;
   }
@@ -709,7 +712,7 @@ static int enc_impl(Enc* e, const float* wav, int B, int n, float* out, const En
     }
     TRY(launch_act<DT>(bk.a, w.X, C, len, B, A, st));
     const int s = bk.s, p = s / 2 + s % 2;
-    const int nout = (len + 2 * p - 2 * s) / s + 1;
+    const int nout = enc_stride_len(len, s);
     FL_REQUIRE(nout > 0, "flamed_enc_encode: input too short for the stride-%d stage", s);
     TRY((enc_gemm<DT>(LoadConvStride<DT>{A, C, len, nout, s, p}, (const DT*)bk.wc, 2 * s * C, EpiBiasAct<float, 0>{bk.bc, w.X, bk.cout},
                       B * nout, bk.cout, 2 * s * C, st)));

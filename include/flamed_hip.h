@@ -367,7 +367,8 @@ FLAMED_API int flamed_enc_create(int ngf, int n_down, const int* ratios, int out
 FLAMED_API int flamed_enc_destroy(flamed_enc_t h);
 FLAMED_API int flamed_enc_num_weights(flamed_enc_t h);
 FLAMED_API int flamed_enc_load(flamed_enc_t h, const float* const* weights, int n_weights, hipStream_t stream);
-/* Output frames for an n-sample input (Conv1d length arithmetic at every stride); -1 for a bad handle. */
+/* Output frames for an n-sample input (Conv1d length arithmetic at every stride); 0 when n is too short for the
+   stride chain (flamed_enc_encode refuses such an input); -1 for a bad handle. */
 FLAMED_API int flamed_enc_out_len(flamed_enc_t h, int n);
 FLAMED_API size_t flamed_enc_workspace_size(flamed_enc_t h, int B, int n);
 /* wav: (B, n) fp32 (the reference's (B, 1, n)); out: (B, out_channels, flamed_enc_out_len(n)) fp32. */

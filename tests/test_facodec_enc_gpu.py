@@ -2,13 +2,17 @@
 Tolerances: exact-fp32 MFMA mode rel-L2 <= 2e-5 (reassociation only) and the RVQ codes computed from
 it bit-identical to the reference's; bf16 mode: error vs the fp32 reference within 1 dB of what the
 reference itself reaches under CPU bf16 autocast (rel-L2 <= 1.122 x, as the decoder test); graph
-replay == eager bitwise."""
+replay == eager bitwise.
+Frame profile (tests/_codecprofile.py; weight-norm gains x the `facodec_calm` gain, as the decoder's profile
+tests): no output frame of the bf16 mode stands further from the oracle than 1.2 x the worst frame of the bf16
+emulation on the same inputs; the f32 mode holds every frame within F32_FRAME_BAR (1e-5)."""
 import numpy as np
 import pytest
 import torch
 
 from _common import golden, seeded, t32, rel_l2, orc
 from _flamed_common import build_codec_encoder
+from _codecprofile import emulated_encode, frame_errors, assert_frame_profile, F32_FRAME_BAR
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -104,3 +108,127 @@ def test_vq_timbre_vs_oracle(B, T):
         assert rel_l2(outs.cpu(), couts) < 1e-4
         for a, b in zip(qb, cqb):
             assert rel_l2(a.cpu(), b) < 1e-4
+
+
+# ------------------------------------------------------------------------------------------------------------
+# frame profiles at the edges (tests/_codecprofile.py)
+# ------------------------------------------------------------------------------------------------------------
+F32_REL = 2e-5  # the file's f32 bar, here per utterance; every frame: F32_FRAME_BAR (20 x the oracle's own
+                # reassociation noise, tests/_codecprofile.py)
+
+
+@pytest.fixture(scope="module")
+def calm_enc():
+    from flamed.utils.seeded_init import scale_weight_norm_gains
+    sd = scale_weight_norm_gains(seeded("facodec_encoder"), float(golden("facodec_calm")["gain"]))
+    encs = {}
+    for mode in ("f32", "bf16"):
+        e = build_codec_encoder("cpu")
+        e.load_state_dict(sd)
+        e.hip_dtype = mode
+        encs[mode] = e.to(DEV)
+    return encs, sd
+
+
+_cases = {}
+
+
+def _case(sd, B, n, seed=0):
+    """(wav, oracle, bf16 emulation) of one seeded input, computed once per run."""
+    key = (B, n, seed)
+    if key not in _cases:
+        wav = 0.1 * torch.randn(B, 1, n, generator=torch.Generator().manual_seed(1000 * B + n + 7919 * seed))
+        _cases[key] = (wav, orc.facodec_encode(sd, wav), emulated_encode(sd, wav))
+    return _cases[key]
+
+
+def _encode(e, wav):
+    with torch.inference_mode():
+        z = e(wav.to(DEV)).cpu()
+    assert e._hip is not None and e._hip.dtype_name == e.hip_dtype  # the HIP path ran
+    return z
+
+
+def _check(mode, z, ref, floor, label):
+    assert z.shape == ref.shape
+    if mode == "f32":
+        rels = [rel_l2(z[i], ref[i]) for i in range(z.shape[0])]
+        e = frame_errors(z, ref)
+        print(f"{label} f32: rel-L2 per utterance max {max(rels):.2e}, frame max {float(e.max()):.2e}, "
+              f"median {float(e.median()):.2e}")
+        assert max(rels) < F32_REL
+        assert float(e.max()) <= F32_FRAME_BAR
+    else:
+        assert_frame_profile(z, ref, floor, f"{label} bf16")
+
+
+# stage lengths floor(n / 2), floor(. / 4), floor((. + 1) / 5), floor((. + 1) / 5)
+ENC_EDGE_SHAPES = [
+    (1, 152),   # the shortest legal input, one output frame
+    (3, 152),   # the same with utterance edges
+    (2, 1001),  # odd remainders at every stride
+    (3, 2055),  # an utterance edge inside every tile size; the first-stage C = 32 path at 6,165 rows
+    (2, 8137),  # the odd length of test_encode_odd_lengths_vs_oracle, batched
+]
+
+
+@pytest.mark.parametrize("B,n", ENC_EDGE_SHAPES)
+@pytest.mark.parametrize("mode", ["f32", "bf16"])
+def test_encode_edge_profiles(calm_enc, mode, B, n):
+    encs, sd = calm_enc
+    wav, ref, floor = _case(sd, B, n)
+    _check(mode, _encode(encs[mode], wav), ref, floor, f"edge {B}x{n}")
+
+
+@pytest.mark.parametrize("mode", ["f32", "bf16"])
+def test_encode_too_short_raises(calm_enc, mode):
+    """152 samples are the shortest input the stride chain accepts (152 -> 76 -> 19 -> 4 -> 1); 151 leave 3 samples
+    to the last k10 conv, which does not fit (the oracle's conv1d raises): ValueError before any launch."""
+    encs, sd = calm_enc
+    e = encs[mode]
+    for B in (1, 3):
+        with pytest.raises(ValueError, match="too short"), torch.inference_mode():
+            e(torch.zeros(B, 1, 151, device=DEV))
+        with pytest.raises(RuntimeError):
+            orc.facodec_encode(sd, torch.zeros(B, 1, 151))
+        assert _encode(e, _case(sd, B, 152)[0]).shape == (B, 256, 1)
+    assert e._hip.out_len(151) == 0 and e._hip.out_len(1) == 0 and e._hip.out_len(152) == 1
+
+
+@pytest.mark.parametrize("mode", ["f32", "bf16"])
+def test_encode_batch_isolation(calm_enc, mode):
+    """As test_decode_batch_isolation, at (3, 1001)."""
+    encs, sd = calm_enc
+    e = encs[mode]
+    B, n = 3, 1001
+    wav, ref, floor = _case(sd, B, n)
+    wavb = wav.clone()
+    wavb[1] = _case(sd, B, n, seed=1)[0][1]
+    a, b = _encode(e, wav), _encode(e, wavb)
+    assert not torch.equal(a[1], b[1])
+    assert torch.equal(a[0], b[0]) and torch.equal(a[2], b[2]), "an utterance changed with its neighbour"
+    for i in range(B):
+        alone = _encode(e, wav[i:i + 1])
+        _check(mode, alone, ref[i:i + 1], floor[i:i + 1], f"isolation {B}x{n} utterance {i} alone")
+        if mode == "f32":
+            assert rel_l2(alone[0], a[i]) < F32_REL
+
+
+@pytest.mark.parametrize("mode", ["f32", "bf16"])
+def test_encode_shape_sequence_no_stale_state(calm_enc, mode):
+    """(1, 152) -> (3, 2055) -> (1, 152) on one handle, graph on then off: the third result equals the first
+    bitwise."""
+    encs, sd = calm_enc
+    e = encs[mode]
+    wav = _case(sd, 1, 152)[0]
+    big = _case(sd, 3, 2055, seed=2)[0]
+    try:
+        for graph in (True, False):
+            e.hip_graph = graph
+            first = _encode(e, wav)
+            mid = _encode(e, big)
+            third = _encode(e, wav)
+            assert mid.shape == (3, 256, 10) and torch.isfinite(mid).all()
+            assert torch.equal(first, third), f"graph={graph}"
+    finally:
+        e.hip_graph = True
