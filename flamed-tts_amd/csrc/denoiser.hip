@@ -1446,6 +1446,14 @@ __global__ void taps_t_kernel(const float* __restrict__ src, float* __restrict__
   const int c = i / KS, j = i - (size_t)c * KS;
   dst[(size_t)j * H + c] = src[i];
 }
+// The same taps channel-major, rows padded to 32 floats (tap KS..31 = 0): the persistent solve's threads read their
+// channel's taps as 16-B loads (KS <= 32).
+__global__ void taps_cm_kernel(const float* __restrict__ src, float* __restrict__ dst, int H, int KS) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)H * 32) return;
+  const int c = i / 32, j = i % 32;
+  dst[i] = j < KS ? src[(size_t)c * KS + j] : 0.f;
+}
 
 __global__ void cast_kernel_bf16(const float* __restrict__ src, bf16* __restrict__ dst, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1738,6 +1746,7 @@ struct DenBlockW {
   const unsigned char* q[4] = {nullptr, nullptr, nullptr, nullptr};
   const unsigned char* qs[4] = {nullptr, nullptr, nullptr, nullptr};
   const float *b2, *b3, *mb0, *mb2, *lnw, *lnb, *lnmw, *lnmb, *dww, *dwb, *gnw, *gnb;
+  const float* dwc = nullptr;  // the depthwise taps channel-major, (H, 32) zero-padded (persistent solve; KS <= 32)
 };
 
 struct Den {
@@ -2075,6 +2084,8 @@ FLAMED_API int flamed_den_load(flamed_den_t h, const float* const* w, int n, hip
   size_t o_out = take(es * (size_t)C * 3 * H);
   std::vector<size_t> o_dw(NB + 1);
   for (int i = 0; i <= NB; ++i) o_dw[i] = take(4ull * KS * H);
+  std::vector<size_t> o_dwc(NB + 1);
+  for (int i = 0; i <= NB; ++i) o_dwc[i] = take(4ull * 32 * H);
   const size_t n_vec = 1 + 11ull * NB + 5;  // H-wide vectors: proj_in bias, 11 per block, 5 final
   const size_t o_vec = take(4ull * (n_vec * H + C));
   const size_t q_bytes = (size_t)H * H + mx_scale_bytes(H, H);  // one fp8 matrix + its scale image
@@ -2108,6 +2119,14 @@ FLAMED_API int flamed_den_load(flamed_den_t h, const float* const* w, int n, hip
   };
   int rc;
 #define TRY(x) do { if ((rc = (x)) != kOk) return rc; } while (0)
+  auto taps_cm = [&](size_t o, const float* src, const float** dst) -> int {
+    *dst = nullptr;
+    if (KS > 32) return kOk;
+    hipLaunchKernelGGL(taps_cm_kernel, dim3((H * 32 + 255) / 256), dim3(256), 0, st, src, reinterpret_cast<float*>(base + o), H, KS);
+    FL_LAUNCH_CHECK();
+    *dst = reinterpret_cast<const float*>(base + o);
+    return kOk;
+  };
   size_t vcur = o_vec;
   auto vec = [&](const float* src, size_t n, const float** dst) -> int {
     TRY(cpy(vcur, src, n));
@@ -2140,6 +2159,7 @@ FLAMED_API int flamed_den_load(flamed_den_t h, const float* const* w, int n, hip
     hipLaunchKernelGGL(taps_t_kernel, dim3((H * KS + 255) / 256), dim3(256), 0, st, bw[4], reinterpret_cast<float*>(base + o_dw[i]), H, KS);
     FL_LAUNCH_CHECK();
     B.dww = reinterpret_cast<float*>(base + o_dw[i]);
+    TRY(taps_cm(o_dwc[i], bw[4], &B.dwc));
     TRY(vec(bw[2], H, &B.lnw)); TRY(vec(bw[3], H, &B.lnb)); TRY(vec(bw[5], H, &B.dwb)); TRY(vec(bw[6], H, &B.gnw));
     TRY(vec(bw[7], H, &B.gnb)); TRY(vec(bw[9], H, &B.b2)); TRY(vec(bw[11], H, &B.b3)); TRY(vec(bw[12], H, &B.lnmw));
     TRY(vec(bw[13], H, &B.lnmb)); TRY(vec(bw[15], H, &B.mb0)); TRY(vec(bw[17], H, &B.mb2));
@@ -2152,6 +2172,7 @@ FLAMED_API int flamed_den_load(flamed_den_t h, const float* const* w, int n, hip
     hipLaunchKernelGGL(taps_t_kernel, dim3((H * KS + 255) / 256), dim3(256), 0, st, fw[2], reinterpret_cast<float*>(base + o_dw[NB]), H, KS);
     FL_LAUNCH_CHECK();
     F.dww = reinterpret_cast<float*>(base + o_dw[NB]);
+    TRY(taps_cm(o_dwc[NB], fw[2], &F.dwc));
     TRY(vec(fw[3], H, &F.dwb)); TRY(vec(fw[4], H, &F.gnw)); TRY(vec(fw[5], H, &F.gnb));
     TRY(cast(o_fin, fw[6], (size_t)H * H)); TRY(vec(fw[7], H, &F.b2));
     TRY(cast(o_fin + es * H * H, fw[8], (size_t)H * H)); TRY(vec(fw[9], H, &F.b3));
@@ -2534,7 +2555,7 @@ static size_t persist_layout(char* base, pk::Params* P) {
   char* xa = take(T * H * 2);
   char* xs = take(T * C * 2);
   char* gnp = take((size_t)pk::kGroups * H * 16);
-  char* yb = take((size_t)pk::kWGs * 16 * 4);
+  char* yb = take((size_t)pk::kWGs * 2 * pk::kCh * 8);  // 16 granules of 8 B per workgroup
   char* xbase = take(T * C * 4);  // two-stage solvers, >= 3 chunks per group: the step's base x (last: the others stay put)
   if (P) {
     P->ctr = reinterpret_cast<int*>(ctr);
@@ -2548,7 +2569,7 @@ static size_t persist_layout(char* base, pk::Params* P) {
     P->xa = reinterpret_cast<bf16*>(xa);
     P->xs = reinterpret_cast<bf16*>(xs);
     P->gnp = reinterpret_cast<float4*>(gnp);
-    P->yb = reinterpret_cast<float*>(yb);
+    P->yb = reinterpret_cast<unsigned long long*>(yb);
     P->xbase = reinterpret_cast<float*>(xbase);
   }
   return off;
@@ -2597,7 +2618,12 @@ static void persist_poll_fails(Den* d) {
 // zero utterances in the spare row groups (knob persist_pad): the reference's metadata mode batches 4 utterances and
 // leaves a trailing batch of 1..3 (synthesize.py:268-291, 344).  Time is set by the most-loaded group, the same as
 // for the padded size.
+// Diagnostic knob persist_as (2, 4 or 8; 0 = off): a smaller batch runs as that size, so e.g. one utterance can be
+// solved alone in exactly the row partition it has inside a batch of 4 (2 row groups instead of 8) and compared with
+// it bitwise -- the GroupNorm partial sums, and with them the rounding, follow the partition.
 static int persist_batch(int B) {
+  const int as = tn().persist_as;
+  if ((as == 2 || as == 4 || as == 8) && B < as) return as;
   if (B == 3) return 4;
   if (B >= 5 && B <= 7) return 8;
   return B;
@@ -2611,7 +2637,7 @@ static bool persist_eligible(Den* d, int B, int T) {
   // one utterance, or (knob persist_multi) B in {2, 4, 8}, each utterance's frames split over its 8 / B row groups;
   // a group holds up to kMaxNTW chunks of 64 frames (kernel variant by chunk count; knob persist_ntw caps it)
   const int B0 = B;
-  if (B != 1 && tu.persist_multi && tu.persist_pad) B = persist_batch(B);
+  if (tu.persist_multi && tu.persist_pad) B = persist_batch(B);  // (one utterance stays one unless persist_as is set)
   if (B != 1 && (!tu.persist_multi || (B != 2 && B != 4 && B != 8))) return false;
   const int ntw = pk::persist_ntw(B, T, tu.persist_opt);
   // padded to at least 1.5x the batch (B = 5 as 8): the idle utterances cost whole chunks, so only up to persist_pad_ntw
@@ -2662,6 +2688,7 @@ static int persist_solve(Den* d, float* xt, const float* mods, int nfe, int B, i
     o.w2 = reinterpret_cast<const bf16*>(b.w2); o.w3 = reinterpret_cast<const bf16*>(b.w3);
     o.m0 = i < d->NB ? reinterpret_cast<const bf16*>(b.m0) : nullptr;
     o.m2 = i < d->NB ? reinterpret_cast<const bf16*>(b.m2) : nullptr;
+    P.dwc[i] = b.dwc;
     o.b2 = b.b2; o.b3 = b.b3; o.dww = b.dww; o.dwb = b.dwb; o.gnw = b.gnw; o.gnb = b.gnb;
     if (i < d->NB) {
       o.mb0 = b.mb0; o.mb2 = b.mb2; o.lnw = b.lnw; o.lnb = b.lnb; o.lnmw = b.lnmw; o.lnmb = b.lnmb;

@@ -677,37 +677,75 @@ __device__ __forceinline__ void fill_cols(float (&v)[2][4], float x) {
     for (int r = 0; r < 4; ++r) v[nt][r] = x;
 }
 
+// A row's (mean, rstd) from the 32 slots' partials, two lanes per row: this lane holds 16 of them (means mv, M2s
+// qv) and pair(x) returns x + the other lane's x.  Combined as row_stats_from_partials does (tile width 32, eps
+// 1e-6): 16 in order, then the pair add.  One body for every caller, so all of them round alike.
+template <class PairAdd>
+__device__ __forceinline__ float2 combine_row_partials(const float (&mv)[16], const float (&qv)[16], PairAdd pair) {
+  float sm = 0.f;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) sm += mv[k];
+  sm = pair(sm);
+  const float mean = sm * (1.0f / kSlots);
+  float m2 = 0.f;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    const float d = mv[k] - mean;
+    m2 += qv[k] + (float)kCols * d * d;
+  }
+  m2 = pair(m2);
+  return make_float2(mean, 1.0f / sqrtf(m2 * (1.0f / kH) + 1e-6f));
+}
+__device__ __forceinline__ void unpack_row_partials(const u32x4 (&v)[8], float (&mv)[16], float (&qv)[16]) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const float4 f = as_f4(v[k]);
+    mv[2 * k] = f.x; qv[2 * k] = f.y; mv[2 * k + 1] = f.z; qv[2 * k + 1] = f.w;
+  }
+}
+
 // (mean, rstd) of rows [ra, rb) from the 32 slots' partials (sc1 loads), into st[2 (r - rbase)]; two
-// lanes per row (16 partials each), combined as row_stats_from_partials does (tile width 32, eps 1e-6).
+// adjacent lanes per row (16 partials each).
 __device__ __forceinline__ void row_stats(const float2* xpart, int T, int ra, int rb, int rbase, float* st) {
   const int n2 = 2 * (rb - ra);
   const __amdgpu_buffer_rsrc_t rs = rsrc(xpart, (unsigned)T * kSlots * 8);
   for (int idx = opq(threadIdx.x); idx < ((n2 + 63) & ~63); idx += kThreads) {
     const bool act = idx < n2;
     const int row = ra + (act ? idx >> 1 : 0), half = idx & 1;
+    u32x4 v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = ld16(rs, (unsigned)((row * kSlots + half * 16 + 2 * k) * 8));
     float mv[16], qv[16];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float4 v = as_f4(ld16(rs, (unsigned)((row * kSlots + half * 16 + 2 * k) * 8)));
-      mv[2 * k] = v.x; qv[2 * k] = v.y; mv[2 * k + 1] = v.z; qv[2 * k + 1] = v.w;
-    }
-    float sm = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) sm += mv[k];
-    sm = dpp_add<kDppXor1>(sm);
-    const float mean = sm * (1.0f / kSlots);
-    float m2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const float d = mv[k] - mean;
-      m2 += qv[k] + (float)kCols * d * d;
-    }
-    m2 = dpp_add<kDppXor1>(m2);
+    unpack_row_partials(v, mv, qv);
+    const float2 ms = combine_row_partials(mv, qv, [](float x) { return dpp_add<kDppXor1>(x); });
     if (act && half == 0) {
-      st[2 * (row - rbase)] = mean;
-      st[2 * (row - rbase) + 1] = 1.0f / sqrtf(m2 * (1.0f / kH) + 1e-6f);
+      st[2 * (row - rbase)] = ms.x;
+      st[2 * (row - rbase) + 1] = ms.y;
     }
   }
+}
+
+// The same statistics for a GEMM epilogue in the transposed layout (lane (c, q) holds row 16 tile + c), without LDS
+// or a barrier, in two parts so the combine can follow the MFMA loop that the loads precede: lanes (c, 0) and
+// (c, 1) each load 16 of their row's 32 partials (sc1, to registers; every other lane and rows >= nr load from past
+// the buffer range: zeros, no memory traffic) ...
+__device__ __forceinline__ void load_row_partials(u32x4 (&v)[8], const float2* xpart, int T, int r0, int nr, int tile,
+                                                  int lane_in) {
+  const int lane = opq(lane_in);
+  const int c = lane & 15, q = lane >> 4, row = 16 * tile + c;
+  const __amdgpu_buffer_rsrc_t rs = rsrc(xpart, (unsigned)T * kSlots * 8);
+  const unsigned base = q < 2 && row < nr ? (unsigned)(((r0 + row) * kSlots + q * 16) * 8) : 0x7ff00000u;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) v[k] = ld16(rs, base + 16 * k);
+}
+// ... and combine them exactly as row_stats does (two halves of 16 in order, then the add across the lane pair,
+// here lanes c and c + 16); lane (c, 0)'s result goes to the row's four lanes.
+__device__ __forceinline__ float2 finish_row_partials(const u32x4 (&v)[8], int lane_in) {
+  float mv[16], qv[16];
+  unpack_row_partials(v, mv, qv);
+  const float2 ms = combine_row_partials(mv, qv, [](float x) { return x + __shfl_xor(x, 16); });
+  const int c = lane_in & 15;
+  return make_float2(__shfl(ms.x, c), __shfl(ms.y, c));
 }
 
 // A staged tile (the GroupNorm apply's bf16 rows: thread -> channel, not an MFMA layout) written through with 16-B sc1
@@ -796,6 +834,9 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
   }
   constexpr bool xloc = false;  // (plain stores kept for an XCD-local group layout; every hand-off is write-through)
   const bool frag = (P.opt & 64) != 0;        // fragment-major GEMM A images (a2, u, xa, xs)
+  // mlp.0 / conv_out: the epilogue's row statistics combined after the MFMA loop (load_row_partials), one chunk; the
+  // 2 x 2 wave-split variant keeps the LDS table (with the eight loads held across gemm_kh it spills)
+  constexpr bool kDefer = NTW == 1 && !KH;
   const bool gran = (P.opt & 512) != 0;       // GroupNorm partials as tagged granules (gnp zeroed per launch)
   int r0, nr;
   group_rows(g, T, P.B, r0, nr, P.opt);
@@ -922,8 +963,8 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
   auto seal_wait = [&](int g0, int ng) -> bool {
     if (dseal) {
       if (wave == 0) {
-        // one load per lane: the group's 32 seals (twice), or for the all-group waits (depthwise halo, Euler
-        // boundary rows) the seals of the two neighbouring groups whose rows this workgroup reads
+        // one load per lane: the group's 32 seals (twice), or for the all-group wait (depthwise halo) the seals of
+        // the two neighbouring groups whose rows this workgroup reads
         const int gi = ng == 1 ? g0 : (lane < 32 ? (g + kGroups - 1) % kGroups : (g + 1) % kGroups);
         dseal_v = __hip_atomic_load(P.seal + 4 * (gi * kSlots + (lane & 31)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         dseal_tgt = L;
@@ -986,7 +1027,7 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
     signal(mygrp);
     ++L;
   };
-  // ---- reset prologue: this launch zeroes its own counter block (and the GroupNorm granule tags), so no
+  // ---- reset prologue: this launch zeroes its own counter block (and the granule tags), so no
   // host memset node has to be ordered before the kernel (a memset node replayed in a captured graph did not
   // reset the counters of later replays).  Two grid-wide arrivals on monotonic counters that are never
   // reset: the first says every workgroup of this launch has started (so the previous launch, stream-
@@ -1007,6 +1048,10 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
       if (gran && tid < 32) {  // 512 B of the 128 KB granule block per workgroup
         const __amdgpu_buffer_rsrc_t rq = rsrc(P.gnp, kGroups * kH * 16);
         st16(rq, (unsigned)((blockIdx.x * 32 + tid) * 16), u32x4{0u, 0u, 0u, 0u});
+      }
+      if (tid < 8) {  // ... and this workgroup's 16 Euler boundary granules (128 B): no tag of an earlier launch survives
+        const __amdgpu_buffer_rsrc_t ry = rsrc(P.yb, kWGs * 2 * kCh * 8);
+        st16(ry, (unsigned)((blockIdx.x * 8 + tid) * 16), u32x4{0u, 0u, 0u, 0u});
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -1031,6 +1076,19 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
     }
   }
   publish_xs();
+
+  // Euler boundary exchange: conv_out's Y0 of a workgroup's last row and Y2 of its first, 8 channels each, as 16
+  // {tag, fp32} granules per workgroup; gp / gn_ = the groups owning frames r0 - 1 / r0 + nr (nearest non-empty
+  // neighbours), read only where that frame belongs to this utterance (empty groups and idle utterances take no part)
+  unsigned long long* const ybq = P.yb;
+  int gp = 0, gn_ = 0;
+  for (int k = 0; k < kGroups; ++k) {
+    int a, b;
+    group_rows(k, T, P.B, a, b, P.opt);
+    if (b > 0 && a + b == r0) gp = k;
+    if (b > 0 && a == r0 + nr) gn_ = k;
+  }
+  const bool ynb_p = !idle && nr > 0 && r0 > ub, ynb_n = !idle && nr > 0 && r0 + nr < ue;
 
   float X[NTW][2][4];  // residual stream tiles (this wave's tiles wave + 4 i: 16 rows x 32 columns each), MFMA layout
 
@@ -1094,13 +1152,32 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
       // raw loads only before the wait (the arithmetic that consumes them after it: computed here, the compiler
       // put the loads' wait ahead of the poll instead of behind it)
       float hsc[4], hsh[4], hlw[4], hlb[4], osc[2][4], osh[2][4], olw[2][4], olb[2][4];
+      // Wide loads before the wait, up to four chunks per group: the halo item's 4 columns as one 16-B load per vector
+      // and the taps from the channel-major copy (B = 1 T = 400: 20 537 -> 20 996 frames/s, B = 4 T = 400 43.2 -> 42.3
+      // ms).  The variants with five or more chunks keep the scalar loads: they spill, and with the wide loads
+      // T = 2400 nfe 256 (five chunks) measured 110.4 ms against 106.4 (profiles/handoff_trim_ab.txt).
+      constexpr bool kWide = NTW <= 4;
+      if constexpr (!kWide) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int col = col0 + 4 * (tid & 7) + e;
-        hsc[e] = mb[H + col];
-        hsh[e] = mb[col];
-        hlw[e] = fin ? 1.0f : bw.lnw[col];
-        hlb[e] = fin ? 0.0f : bw.lnb[col];
+        for (int e = 0; e < 4; ++e) {
+          const int col = col0 + 4 * (tid & 7) + e;
+          hsc[e] = mb[H + col];
+          hsh[e] = mb[col];
+          hlw[e] = fin ? 1.0f : bw.lnw[col];
+          hlb[e] = fin ? 0.0f : bw.lnb[col];
+        }
+      } else {  // (col0 + 4 (tid & 7): 16-B aligned as ld_cols' addresses are)
+        const int col = col0 + 4 * (tid & 7);
+        const float4 a = *reinterpret_cast<const float4*>(mb + H + col), b = *reinterpret_cast<const float4*>(mb + col);
+        hsc[0] = a.x; hsc[1] = a.y; hsc[2] = a.z; hsc[3] = a.w;
+        hsh[0] = b.x; hsh[1] = b.y; hsh[2] = b.z; hsh[3] = b.w;
+        float4 lw = make_float4(1.0f, 1.0f, 1.0f, 1.0f), lb = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (!fin) {
+          lw = *reinterpret_cast<const float4*>(bw.lnw + col);
+          lb = *reinterpret_cast<const float4*>(bw.lnb + col);
+        }
+        hlw[0] = lw.x; hlw[1] = lw.y; hlw[2] = lw.z; hlw[3] = lw.w;
+        hlb[0] = lb.x; hlb[1] = lb.y; hlb[2] = lb.z; hlb[3] = lb.w;
       }
       ld_cols(osc, mb + H + col0, q);  // the lane's own columns (transposed layout)
       ld_cols(osh, mb + col0, q);
@@ -1111,9 +1188,19 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
         ld_cols(olw, bw.lnw + col0, q);
         ld_cols(olb, bw.lnb + col0, q);
       }
-      float w[kTaps];
+      float w[kTaps];  // channel cc's taps
+      if constexpr (kWide) {  // from the channel-major copy: eight 16-B loads (tap 31 is padding)
+        const float4* wp = reinterpret_cast<const float4*>(P.dwc[blk] + (size_t)(col0 + cc) * 32);
 #pragma unroll
-      for (int j = 0; j < kTaps; ++j) w[j] = bw.dww[(size_t)j * H + col0 + cc];
+        for (int j = 0; j < 8; ++j) {
+          const float4 t = wp[j];
+          w[4 * j] = t.x; w[4 * j + 1] = t.y; w[4 * j + 2] = t.z;
+          if (4 * j + 3 < kTaps) w[4 * j + 3] = t.w;
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < kTaps; ++j) w[j] = bw.dww[(size_t)j * H + col0 + cc];
+      }
       const float dbias = bw.dwb[col0 + cc];
       float gwv = 0.f, gbv = 0.f;
       if (tid < kCols) {
@@ -1464,9 +1551,13 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
       PST(step);
       if (!wait_ge(errw, fails, tmo, mygrp, 0, 1, 32 * L, flag) || !seal_wait(g, 1)) { fail_exit(); return; }
       PST(step);
-      // the epilogue's row statistics of x (conv_3's partials) before the GEMM (issued between the GEMM's A loads and
-      // their wait instead, r06j measured 20.84 vs 20.63 ms per B = 1 solve: slower)
-      row_stats(P.xpart[1], TT, r0, r0 + nr, r0 - kHalo, st);
+      // the epilogue's row statistics of x (conv_3's partials).  One chunk: only their loads go out here, ahead of the
+      // A loads; the combine follows the MFMA loop, which does not need it (load_row_partials).  Several chunks: the
+      // LDS table before the GEMM (issued between the GEMM's A loads and their wait instead, r06j measured 20.84 vs
+      // 20.63 ms per B = 1 solve: slower)
+      [[maybe_unused]] u32x4 rp_m0[8];
+      if constexpr (kDefer) load_row_partials(rp_m0, P.xpart[1], TT, r0, nr, wave, lane);
+      else row_stats(P.xpart[1], TT, r0, r0 + nr, r0 - kHalo, st);
       f32x4 accm_m0[NTW][2];  // every tile's products (several chunks: one streamed pass, epilogues after it)
       if constexpr (KH) gemm_kh<kH>(P.xa, r0, nr, (smem + wb * kWPanel), accm_m0[0], wave, lane, PSTP(step), g, frag);
       else if constexpr (NTW == 1) gemm<kH>(P.xa, r0, nr, (smem + wb * kWPanel), accm_m0[0], wave, lane, PSTP(step), g, frag);
@@ -1477,8 +1568,16 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
         const int tl = wave + 4 * ci;
         const f32x4(&acc)[2] = accm_m0[ci];
         float v[2][4];
-        const int p = 16 * tl + c + kHalo;  // the lane's row (transposed layout)
-        const float mean = st[2 * p], rstd = st[2 * p + 1];
+        float mean, rstd;  // of the lane's row (transposed layout)
+        if constexpr (kDefer) {
+          const float2 ms = finish_row_partials(rp_m0, lane);
+          mean = ms.x;
+          rstd = ms.y;
+        } else {
+          const int p = 16 * tl + c + kHalo;
+          mean = st[2 * p];
+          rstd = st[2 * p + 1];
+        }
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
 #pragma unroll
@@ -1552,7 +1651,9 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
     PST(step);
     if (!wait_ge(errw, fails, tmo, mygrp, 0, 1, 32 * L, flag) || !seal_wait(g, 1)) { fail_exit(); return; }
     PST(step);
-    row_stats(P.xpart[1], TT, r0, r0 + nr, r0 - kHalo, st);
+    [[maybe_unused]] u32x4 rp_out[8];  // row statistics as in mlp.0: loads here, the combine after the MFMA loop
+    if constexpr (kDefer) load_row_partials(rp_out, P.xpart[1], TT, r0, nr, wave, lane);
+    else row_stats(P.xpart[1], TT, r0, r0 + nr, r0 - kHalo, st);
     f32x4 acco[NTW][2];  // every tile's products first: with several chunks Y goes into this phase's panel buffer
     if constexpr (KH) gemm_kh<kH>(P.xa, r0, nr, (smem + wb * kWPanel), acco[0], wave, lane, PSTP(step), g, frag);
     else if constexpr (NTW == 1) gemm<kH>(P.xa, r0, nr, (smem + wb * kWPanel), acco[0], wave, lane, PSTP(step), g, frag);
@@ -1567,7 +1668,15 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
     for (int ci = 0; ci < NTW; ++ci) {
       const int row = 16 * (wave + 4 * ci) + c, p = row + kHalo;  // the lane's row (transposed layout)
       if (NTW == 1 || row < nr) {
-        const float mean = st[2 * p], rstd = st[2 * p + 1];
+        float mean, rstd;
+        if constexpr (kDefer) {
+          const float2 ms = finish_row_partials(rp_out, lane);
+          mean = ms.x;
+          rstd = ms.y;
+        } else {
+          mean = st[2 * p];
+          rstd = st[2 * p + 1];
+        }
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
           const int n0 = 16 * nt + 4 * q;  // the lane's 4 stacked columns (n >= 24 repeat 0..7: not stored)
@@ -1582,55 +1691,72 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
     }
     __syncthreads();
     // publish what the neighbouring groups' Euler updates need: Y0 of the last frame, Y2 of the first
-    if (tid < 4 && nr > 0) {
-      const __amdgpu_buffer_rsrc_t ry = rsrc(P.yb, kWGs * 16 * 4);
-      const int half = tid >> 1, k = tid & 1;
-      const float* src = half == 0 ? yl + (nr - 1) * 24 + 4 * k : yl + 16 + 4 * k;
-      st16(ry, (unsigned)(((g + kGroups * s) * 16 + half * 8 + 4 * k) * 4), __builtin_bit_cast(u32x4, *reinterpret_cast<const float4*>(src)));
+    // as tagged granules (the data is the flag: no drain, no counter, no seal -- a granule validates itself)
+    const unsigned ytag = (unsigned)(step - P.s0 + 1);  // this launch's evaluation number, never 0
+    if (tid < 2 * kCh && nr > 0 && !idle) {
+      const float y = tid < kCh ? yl[(nr - 1) * 24 + tid] : yl[16 + tid - kCh];
+      __hip_atomic_store(ybq + (size_t)(g + kGroups * s) * (2 * kCh) + tid, ((unsigned long long)ytag << 32) | __float_as_uint(y),
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    seal_put();
-    if (dmafirst && step + 1 < P.s1) {
-      next_win();
-      signal_dma<4>(mygrp);
-    } else {
-      signal(mygrp);
-      if (step + 1 < P.s1) next_win();
-    }
+    if (step + 1 < P.s1) next_win();
     PST(step);
-    ++L;
 
     // -------- Euler update x += dt * v, v[t] = b + Y1[t] + Y0[t-1] + Y2[t+1] (:445; conv3_combine order)
+    // The two boundary rows come from the same-slot workgroups of the neighbouring groups only: wave 0 re-reads
+    // their granules (lanes 0..7: Y0 of gp's last row, 8..15: Y2 of gn_'s first) until every tag is this
+    // evaluation's.  Write after read: a neighbour rewrites its granules only in the next evaluation's conv_out,
+    // which lies behind that evaluation's grid-wide GroupNorm exchanges, and this workgroup (the neighbour's slot:
+    // a party to those exchanges) enters them only after the read below.
     PST(step);
-    if (!wait_ge(errw, fails, tmo, grp, 16, kGroups, 32 * L, flag) || !seal_wait(0, kGroups)) { fail_exit(); return; }
-    PST(step);
-    int gp = 0, gn_ = 0;  // the groups owning frames r0 - 1 and r0 + nr (nearest non-empty neighbours)
-    for (int k = 0; k < kGroups; ++k) {
-      int a, b;
-      group_rows(k, T, P.B, a, b, P.opt);
-      if (b > 0 && a + b == r0) gp = k;
-      if (b > 0 && a == r0 + nr) gn_ = k;
+    if (ynb_p || ynb_n) {
+      if (tid < 64) {
+        const bool need = tid < kCh ? ynb_p : tid < 2 * kCh && ynb_n;
+        const unsigned long long* yq = ybq + (size_t)((tid < kCh ? gp : gn_) + kGroups * s) * (2 * kCh) + (tid & (2 * kCh - 1));
+        float y = 0.f;
+        bool ok = true;
+        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+        for (unsigned it = 0;; ++it) {
+          bool mine = true;
+          if (need) {
+            const unsigned long long a = __hip_atomic_load(yq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            mine = (unsigned)(a >> 32) == ytag;
+            y = __uint_as_float((unsigned)a);
+          }
+          if (__all(mine)) break;
+          if ((it & 31) == 31) {
+            if (__hip_atomic_load(errw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) { ok = false; break; }
+            if ((long long)(__builtin_amdgcn_s_memrealtime() - t0) > tmo) {
+              if (tid == 0) raise_err(errw, fails, 1);
+              ok = false;
+              break;
+            }
+          }
+          __builtin_amdgcn_s_sleep(1);
+        }
+        if (tid == 0) *flag = ok ? 1 : 0;
+        if (tid < 2 * kCh) red[tid] = y;
+      }
+      __syncthreads();
+      if (*flag == 0) { fail_exit(); return; }  // (the flag is next written behind the barrier that ends this phase)
     }
+    PST(step);
 #pragma unroll
     for (int ci = 0; ci < NTW; ++ci) {
       const int row = kChunk * ci + xr_row;
       if (row < nr) {
         const int t = r0 + row;
-        const __amdgpu_buffer_rsrc_t ry = rsrc(P.yb, kWGs * 16 * 4);
         float vv[2];
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
           const int chl = 2 * (tid & 3) + e, ch = kCh * s + chl;
           float v = P.bout[ch] + yl[row * 24 + 8 + chl];
           if (t > ub) {  // zero padding at the utterance's edges (conv_out k3)
-            const float y0 = row > 0 ? yl[(row - 1) * 24 + chl]
-                                     : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                           ry, (unsigned)(((gp + kGroups * s) * 16 + chl) * 4), 0, 16));
+            // (an idle utterance exchanges nothing: its edge rows take 0)
+            const float y0 = row > 0 ? yl[(row - 1) * 24 + chl] : ynb_p ? red[chl] : 0.f;
             v += y0;
           }
           if (t < ue - 1) {
-            const float y2 = row < nr - 1 ? yl[(row + 1) * 24 + 16 + chl]
-                                          : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                ry, (unsigned)(((gn_ + kGroups * s) * 16 + 8 + chl) * 4), 0, 16));
+            const float y2 = row < nr - 1 ? yl[(row + 1) * 24 + 16 + chl] : ynb_n ? red[kCh + chl] : 0.f;
             v += y2;
           }
           vv[e] = v;

@@ -19,12 +19,20 @@
 // the exact register image of a v_mfma_f32_16x16x32_bf16 A operand, so each consumer wave's load of one
 // K-step is one contiguous 1 KB (8 full lines) instead of 16 rows x 64 B (16 half-lines): the per-XCD L2
 // request rate, not bytes, was what the A fetch waited on (2.4 -> 1.2 us per GEMM phase, 26.4 -> 22.8 ms).
-// Every activation handed to another workgroup (bf16 GEMM operands, LayerNorm row partials, halo rows,
-// GroupNorm partials, conv_out boundary rows) is stored write-through (sc1), drained by every storing
+// Every activation handed to another workgroup through a counter (bf16 GEMM operands, LayerNorm row partials,
+// halo rows) is stored write-through (sc1), drained by every storing
 // wave, then one lane adds to a counter; consumers poll with sc1 loads and read the data with sc1
 // loads only (cdna_hip_programming.md §6 Guideline 16, table row 1: no release / acquire fences).
 //   group counters  grp[g]: the 32 slots of g add 1 after each group phase (GEMM operands, partials)
-//   GroupNorm       gn[s]:  the 8 groups' slot-s workgroups add 1 after publishing their partials
+//   GroupNorm       gn[s]:  the 8 groups' slot-s workgroups add 1 after publishing their partials (the counter form,
+//                           persist_opt without 512)
+// Two exchanges need no drain and no counter: their data is the flag.  Each value travels as an 8-byte {tag, fp32}
+// granule (one relaxed agent-scope atomic store; readers re-read with atomic loads until every tag is the expected
+// one), and the launch's reset prologue zeroes every tag, so none of an earlier launch matches:
+//   GroupNorm partials gnp (persist_opt 512, default): tag = the number of the GroupNorm hand-off
+//   conv_out boundary rows yb: Y0 of a workgroup's last row and Y2 of its first, 8 channels each, read only by the
+//                           same-slot workgroups of the two neighbouring groups; tag = the launch's evaluation number.
+//                           conv_out therefore signals nothing: the Euler update waits for 16 granules, not the grid.
 // Per step: proj_in, 4 x (dwconv+GroupNorm, conv_2, conv_3, mlp.0, mlp.2), FinalLayer (dwconv+
 // GroupNorm, conv_2, conv_3, conv_out), Euler update.  Numerics follow the bf16 launch path (bf16
 // operands, fp32 accumulation / residual / statistics / state, the LayerNorm fold of mlp.0 and
@@ -78,7 +86,7 @@ __host__ __device__ inline bool arrive_reached(unsigned cur, unsigned target) { 
 
 struct BlockW {
   const bf16 *w2, *w3, *m0, *m2;
-  const float *b2, *b3, *mb0, *mb2, *lnw, *lnb, *lnmw, *lnmb, *dww, *dwb, *gnw, *gnb;
+  const float *b2, *b3, *mb0, *mb2, *lnw, *lnb, *lnmw, *lnmb, *dww, *dwb, *gnw, *gnb;  // dww: tap-major (31, H)
 };
 
 struct Params {
@@ -107,7 +115,8 @@ struct Params {
   bf16* xa;                // x * alpha (LayerNorm fold) = mlp.0 / conv_out operand, T x H
   bf16* xs;                // bf16(x) = proj_in operand, T x C
   float4* gnp;             // GroupNorm partials (n, mean, M2) per (group, channel): 8 x H
-  float* yb;               // conv_out boundary rows per workgroup: Y0 of its last row, Y2 of its first
+  unsigned long long* yb;  // conv_out boundary rows per workgroup as {tag, fp32} granules: Y0 of its last row [0, 8),
+                           // Y2 of its first [8, 16); tag = the launch's evaluation number (from 1), zeroed per launch
   int* ctr;
   int* seal;               // persist_opt 16384: per (group, slot) the number of its last group hand-off (16 B each)
   int* sticky;             // kStickyInts words never reset between launches: [SY_FAILS] failed launches so far
@@ -129,6 +138,10 @@ struct Params {
   float adt = 0.f, c1 = 0.f, c2dt = 0.f;
   float* xbase = nullptr;  // the step's base x of the variants with >= 3 chunks per group (B T x C, thread-private
                            // elements: each thread stores and reloads its own)
+  // The depthwise taps of block i once more, channel-major: (H, 32) fp32 with tap 31 zero, which a thread reads as
+  // eight 16-B loads (the kernel variants up to four chunks per group; the others read blk[i].dww).  Last in the
+  // struct: the variants that do not read it see the kernel arguments they always had.
+  const float* dwc[kMaxNB + 1] = {};
 };
 
 // Host side (persist.hip): whether this device runs the 256-workgroup grid fully resident, and the launch.

@@ -220,6 +220,9 @@ FLAMED_API int flamed_den_time_kernels_graph(flamed_den_t h, float* xt, const fl
  *                     in the spare row groups (4 x T / 8 x T <= 4096); 0: those B take the graph of launches;
  *   "persist_pad_ntw" — ... and a batch padded to >= 1.5x its size (B = 5 as 8) only while it needs at most this
  *                     many 64-frame chunks per row group, 1..8 (default 4: B = 5 up to T = 256);
+ *   "persist_as"    — diagnostic, 0 (default = off), 2, 4 or 8: a smaller batch runs padded to this size (needs
+ *                     persist_pad and persist_multi), e.g. one utterance alone in the row partition it has inside a
+ *                     batch of 4, which makes the two bitwise comparable;
  *   "persist_ntw"   — 64-frame chunks per persistent row group, 1..8 (default 8: T <= 4096 at B = 1);
  *   "persist_multi_ntw" — ... and for B > 1, 1..8 (default 8; an A/B knob against the graph of launches);
  *   "persist_capmode" — persistent launch inside a stream capture: 0 (default) cooperative node, 1 plain;
