@@ -134,8 +134,10 @@ struct LoadGNRelu {
 // GroupNorm statistics (F.group_norm, biased variance, eps) of H (B*T x C) for G groups of CG channels
 // over every frame of an utterance: one workgroup per (group, utterance); per-thread Chan partials over
 // a strided slice, combined through LDS in a fixed order (deterministic).
+// mask (flamed_cond_fold_exact; null otherwise): (B, T), only the frames whose mask is not 0 count, and the variance
+// divides by that count.
 __global__ __launch_bounds__(256) void group_stats_kernel(const float* __restrict__ H, int T, int C, int CG, float eps,
-                                                          float* __restrict__ gs) {
+                                                          float* __restrict__ gs, const float* __restrict__ mask) {
   const int g = blockIdx.x, b = blockIdx.y, G = gridDim.x;
   const int tid = threadIdx.x;
   const int c4 = CG / 4;  // float4 chunks per frame (CG % 4 == 0)
@@ -143,6 +145,7 @@ __global__ __launch_bounds__(256) void group_stats_kernel(const float* __restric
   const size_t total = (size_t)T * c4;
   for (size_t i = tid; i < total; i += 256) {
     const int t = i / c4, c = (int)(i - (size_t)t * c4) * 4;
+    if (mask && mask[(size_t)b * T + t] == 0.f) continue;
     const float4 v = ld4(H + ((size_t)b * T + t) * C + (size_t)g * CG + c);
     const float s = v.x + v.y + v.z + v.w;
     const float mb = s * 0.25f;
@@ -199,21 +202,36 @@ __global__ void cf_cast_kernel(const float* __restrict__ src, void* __restrict__
   else reinterpret_cast<float*>(dst)[i] = src[i];
 }
 
+// rows whose mask is 0 -> 0 (a select: whatever the GEMM wrote there, NaN included, is dropped)
+__global__ void cf_zero_masked_kernel(float* __restrict__ out, const float* __restrict__ mask, size_t n, int N) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && mask[i / N] == 0.f) out[i] = 0.f;
+}
+
+// exact: the GroupNorm statistics over the mask's frames only, masked output rows zeroed (flamed_cond_fold_exact)
 template <typename DT>
 static int cond_fold_impl(CondFold* f, const float* cond, const float* mask, int B, int T, float* out, const CondWs& w,
-                          hipStream_t st) {
+                          hipStream_t st, bool exact = false) {
   const int M = B * T;
   int rc;
   const LoadQEnc<DT> xq{cond, f->emb, mask, T, f->Q, f->D};
   if ((rc = launch_gemm<DT>(xq, (const DT*)f->w1, f->C, EpiBiasAct<float, 0>{f->b1, w.H1, f->C}, M, f->C, f->C, st))) return rc;
-  hipLaunchKernelGGL(group_stats_kernel, dim3(f->G, B), dim3(256), 0, st, w.H1, T, f->C, f->C / f->G, 1e-5f, w.S1);
+  hipLaunchKernelGGL(group_stats_kernel, dim3(f->G, B), dim3(256), 0, st, w.H1, T, f->C, f->C / f->G, 1e-5f, w.S1,
+                     exact ? mask : nullptr);
   FL_LAUNCH_CHECK();
   const LoadResMish<DT> lr{xq, w.H1, w.S1, f->g1w, f->g1b, f->C, f->C / f->G};
   if ((rc = launch_gemm<DT>(lr, (const DT*)f->w2, f->C, EpiBiasAct<float, 0>{f->b2, w.H2, f->C2}, M, f->C2, f->C, st))) return rc;
-  hipLaunchKernelGGL(group_stats_kernel, dim3(f->G, B), dim3(256), 0, st, w.H2, T, f->C2, f->C2 / f->G, 1e-5f, w.S2);
+  hipLaunchKernelGGL(group_stats_kernel, dim3(f->G, B), dim3(256), 0, st, w.H2, T, f->C2, f->C2 / f->G, 1e-5f, w.S2,
+                     exact ? mask : nullptr);
   FL_LAUNCH_CHECK();
   const LoadGNRelu<DT> lg{w.H2, w.S2, f->g2w, f->g2b, f->C2, f->C2 / f->G, T};
-  return launch_gemm<DT>(lg, (const DT*)f->w3, f->C2, EpiBiasAct<float, 3>{f->b3, out, f->OUT}, M, f->OUT, f->C2, st);
+  if ((rc = launch_gemm<DT>(lg, (const DT*)f->w3, f->C2, EpiBiasAct<float, 3>{f->b3, out, f->OUT}, M, f->OUT, f->C2, st))) return rc;
+  if (exact) {
+    const size_t n = (size_t)M * f->OUT;
+    hipLaunchKernelGGL(cf_zero_masked_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out, mask, n, f->OUT);
+    FL_LAUNCH_CHECK();
+  }
+  return kOk;
 }
 
 }  // namespace fl
@@ -294,24 +312,34 @@ FLAMED_API size_t flamed_cond_workspace_size(flamed_cond_t h, int B, int T) {
   return f ? cond_ws_layout(f, B, T, nullptr, nullptr) : 0;
 }
 
-FLAMED_API int flamed_cond_fold(flamed_cond_t h, const float* cond, const float* mask, int B, int T, float* out, void* ws,
-                                size_t ws_bytes, hipStream_t st) {
+static int cond_fold_call(flamed_cond_t h, const float* cond, const float* mask, int B, int T, float* out, void* ws,
+                          size_t ws_bytes, hipStream_t st, bool exact, const char* what) {
   CondFold* f = reinterpret_cast<CondFold*>(h);
-  FL_REQUIRE(f && f->dev, "flamed_cond_fold: handle not loaded");
-  FL_REQUIRE(cond && mask && out && ws && B > 0 && T > 0, "flamed_cond_fold: bad args");
+  FL_REQUIRE(f && cond && mask && out && ws && B > 0 && T > 0, "%s: bad args (a null pointer, or B, T < 1)", what);
+  FL_REQUIRE(f->dev, "%s: handle not loaded", what);
   if (ws_bytes < cond_ws_layout(f, B, T, nullptr, nullptr)) {
-    set_error("flamed_cond_fold: workspace too small");
+    set_error("%s: workspace too small", what);
     return kNoWorkspace;
   }
   std::lock_guard<std::mutex> lk(f->mu);
   FL_ON_DEVICE(f->device);
-  FL_REQUIRE_ON(cond, f->device, "flamed_cond_fold");
+  FL_REQUIRE_ON(cond, f->device, what);
   const Tune tsnap = tune_snapshot(nullptr);
   TuneScope ts_(&tsnap);
   CondWs w;
   cond_ws_layout(f, B, T, ws, &w);
-  return f->dt == FLAMED_BF16 ? cond_fold_impl<bf16>(f, cond, mask, B, T, out, w, st)
-                              : cond_fold_impl<float>(f, cond, mask, B, T, out, w, st);
+  return f->dt == FLAMED_BF16 ? cond_fold_impl<bf16>(f, cond, mask, B, T, out, w, st, exact)
+                              : cond_fold_impl<float>(f, cond, mask, B, T, out, w, st, exact);
+}
+
+FLAMED_API int flamed_cond_fold(flamed_cond_t h, const float* cond, const float* mask, int B, int T, float* out, void* ws,
+                                size_t ws_bytes, hipStream_t st) {
+  return cond_fold_call(h, cond, mask, B, T, out, ws, ws_bytes, st, false, "flamed_cond_fold");
+}
+
+FLAMED_API int flamed_cond_fold_exact(flamed_cond_t h, const float* cond, const float* mask, int B, int T, float* out,
+                                      void* ws, size_t ws_bytes, hipStream_t st) {
+  return cond_fold_call(h, cond, mask, B, T, out, ws, ws_bytes, st, true, "flamed_cond_fold_exact");
 }
 
 }  // extern "C"

@@ -2665,8 +2665,10 @@ struct Rk2 {
 // Steps [s0, s1) of a B = 1 solve as ONE cooperative launch, enqueued on `st` with no host synchronisation:
 // the kernel (it resets its own counter block) and, outside a capture, HIP events around it plus an async
 // copy of the sticky failure word.  A failed launch NaN-poisons x and is reported by the next call / persist_info.
+// lens (exact lengths, B host ints in 1..T, several utterances): the ragged kernel variants -- utterance u is solved
+// over its own lens[u] frames; the chunk count follows the longest one.
 static int persist_solve(Den* d, float* xt, const float* mods, int nfe, int B, int T, int s0, int s1, hipStream_t st,
-                         const Rk2* rk = nullptr) {
+                         const Rk2* rk = nullptr, const int* lens = nullptr) {
   const bool cap = stream_capturing(st);
   FL_REQUIRE(d->pmem && d->pfail_host && d->perr_host, "persistent solve: scratch not allocated at load");
   pk::Params P{};
@@ -2699,6 +2701,16 @@ static int persist_solve(Den* d, float* xt, const float* mods, int nfe, int B, i
   P.tmo = 50000000;  // 0.5 s of s_memrealtime (100 MHz) per wait
   P.opt = tn().persist_opt;
   P.ntw = pk::persist_ntw(Bp, T, P.opt);
+  if (lens) {
+    FL_REQUIRE(Bp >= 2 && Bp <= pk::kGroups, "persistent solve: exact lengths take 2..%d utterances", pk::kGroups);
+    int lmax = 1;
+    for (int u = 0; u < Bp; ++u) {
+      P.lens[u] = u < B ? lens[u] : T;  // (idle utterances keep the dense split)
+      FL_REQUIRE(P.lens[u] >= 1 && P.lens[u] <= T, "persistent solve: utterance %d holds %d frames (1..%d)", u, P.lens[u], T);
+      if (u < B && lens[u] > lmax) lmax = lens[u];
+    }
+    P.ntw = pk::persist_ntw(Bp, Bp != B ? T : lmax, P.opt);
+  }
   P.inject_step = tn().persist_inject;
   P.seal_skip = tn().persist_seal_skip;
   hipEvent_t* ev = nullptr;
@@ -2711,7 +2723,7 @@ static int persist_solve(Den* d, float* xt, const float* mods, int nfe, int B, i
   }
   // inside a capture: a cooperative kernel node (persist_capmode 0) or a plain one (1; residency was checked
   // by the uncaptured cooperative launches and persist_device_ok)
-  const int lrc = pk::persist_launch(P, st, !cap || tn().persist_capmode == 0);
+  const int lrc = pk::persist_launch(P, st, !cap || tn().persist_capmode == 0, lens != nullptr);
   if (lrc) return lrc;
   if (!cap) {
     FL_HIP(hipEventRecord(ev[1], st));
@@ -2961,8 +2973,10 @@ static int den_chain_streams(Den* d, int S, hipStream_t st) {
 // (flamed_den_solve_rk2; always the whole solve): two evaluations per step, x and the stage state y (the workspace's
 // XP) alternating as the evaluation's input, each evaluation a den_step with a velocity output (XV) followed by
 // rk2_update_kernel; modulation row block k belongs to evaluation k on every path.
+// mod_B > 0 (the exact-lengths fallback, plain launches only): xt is a sub-batch of B utterances whose modulation rows
+// lie in the table of a batch of mod_B, so row block k starts k * mod_B rows in.
 static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe, int B, int T, void* ws, size_t ws_bytes,
-                           int use_graph, int s0, int s1, const Rk2* rk, hipStream_t st) {
+                           int use_graph, int s0, int s1, const Rk2* rk, hipStream_t st, int mod_B = 0) {
   Den* d = reinterpret_cast<Den*>(h);
   FL_REQUIRE(d && d->dev, "flamed_den_solve: handle not loaded");
   FL_REQUIRE(xt && mods && ws && B > 0 && T > 0 && nfe > 0, "flamed_den_solve: bad args");
@@ -2976,7 +2990,8 @@ static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe
   }
   // delta_t = 1 / nfe as a python float, applied in fp32 (prob_generator.py:441,445)
   const float dt = (float)(1.0 / (double)nfe);
-  const size_t step_stride = (size_t)B * d->MS;
+  FL_REQUIRE(mod_B == 0 || (mod_B >= B && !(use_graph & 1)), "flamed_den_solve: a sub-batch solve runs plain launches");
+  const size_t step_stride = (size_t)(mod_B ? mod_B : B) * d->MS;
   const int S = den_split(d, B, T), Bk = B / S;
   const size_t wsk = S > 1 ? den_split_ws(d, B, T, S) : 0;
   auto sub = [&](int k, float*& xk, const float*& mk, void*& wk) {  // chain k's state, table rows, workspace
@@ -3185,6 +3200,61 @@ FLAMED_API int flamed_den_solve_rk2(flamed_den_t h, float* xt, const float* mods
   FL_REQUIRE(h && xt && mods && ws, "flamed_den_solve_rk2: null handle, state, modulation table or workspace");
   const Rk2 rk(a, nsteps);
   return den_solve_range(h, xt, mods, 2 * nsteps, B, T, ws, ws_bytes, use_graph, 0, 2 * nsteps, &rk, st);
+}
+
+// Exact lengths: utterance u of the padded batch (rows u T .. u T + lens[u] - 1 of xt, modulation row u of every block)
+// solved over its own lens[u] frames, as if alone at T = lens[u]; the rows behind it are neither read nor written.
+//   * every length T: the dense solve itself (bitwise);
+//   * 2..8 utterances eligible for the persistent launch: its ragged variants, one launch;
+//   * anything else (fp32 / fp8 handles, B > 8, the chunk limits, knob persist 0, use_graph bit 2, a device that
+//     refuses the cooperative grid): one utterance after another through the range solver, plain launches against
+//     the whole batch's modulation table.  (Per-utterance lengths inside the launch-path kernels are not built.)
+static int den_solve_lens(flamed_den_t h, float* xt, const float* mods, const int* lens, int nfe, int B, int T, void* ws,
+                          size_t ws_bytes, int use_graph, const Rk2* rk, hipStream_t st, const char* what) {
+  // host-side argument checks, before anything touches the handle or a device
+  FL_REQUIRE(h && xt && mods && lens && ws, "%s: null handle, state, modulation table, lengths or workspace", what);
+  FL_REQUIRE(B > 0 && T > 0 && nfe > 0, "%s: bad args (B = %d, T = %d, %d evaluations)", what, B, T, nfe);
+  bool dense = true;
+  for (int u = 0; u < B; ++u) {
+    // (one frame alone is what the reference's GroupNorm over T refuses)
+    FL_REQUIRE(lens[u] >= 2 && lens[u] <= T, "%s: utterance %d has length %d (2..T = %d)", what, u, lens[u], T);
+    dense = dense && lens[u] == T;
+  }
+  if (dense) return den_solve_range(h, xt, mods, nfe, B, T, ws, ws_bytes, use_graph, 0, nfe, rk, st);
+  // one utterance: the ordinary solve of its first lens[0] rows (the table holds one row per block either way)
+  if (B == 1) return den_solve_range(h, xt, mods, nfe, 1, lens[0], ws, ws_bytes, use_graph, 0, nfe, rk, st);
+  Den* d = reinterpret_cast<Den*>(h);
+  FL_REQUIRE(d->dev, "%s: handle not loaded", what);
+  FL_DEN_CALL(d);
+  FL_REQUIRE_ON(xt, d->device, what);
+  if (ws_bytes < den_solve_ws(d, B, T)) {
+    set_error("%s: workspace too small", what);
+    return kNoWorkspace;
+  }
+  if (B >= 2 && B <= pk::kGroups && !(use_graph & 2) && persist_eligible(d, B, T)) {
+    const int prc = persist_solve(d, xt, mods, nfe, B, T, 0, nfe, st, rk, lens);
+    if (prc != kBadArg) return prc;
+    d->pdev_ok = 0;  // the runtime refused the cooperative grid: this device never runs the persistent solve
+  }
+  for (int u = 0; u < B; ++u) {
+    const int rc = den_solve_range(h, xt + (size_t)u * T * d->C, mods + (size_t)u * d->MS, nfe, 1, lens[u], ws, ws_bytes,
+                                   use_graph & 2, 0, nfe, rk, st, B);
+    if (rc) return rc;
+  }
+  return kOk;
+}
+
+FLAMED_API int flamed_den_solve_lens(flamed_den_t h, float* xt, const float* mods, const int* lens, int nfe, int B, int T,
+                                     void* ws, size_t ws_bytes, int use_graph, hipStream_t st) {
+  return den_solve_lens(h, xt, mods, lens, nfe, B, T, ws, ws_bytes, use_graph, nullptr, st, "flamed_den_solve_lens");
+}
+
+FLAMED_API int flamed_den_solve_rk2_lens(flamed_den_t h, float* xt, const float* mods, const int* lens, int nsteps, double a,
+                                         int B, int T, void* ws, size_t ws_bytes, int use_graph, hipStream_t st) {
+  FL_REQUIRE(nsteps >= 1 && nsteps <= (1 << 29), "flamed_den_solve_rk2_lens: nsteps = %d (at least 1)", nsteps);
+  FL_REQUIRE(a > 0.0 && a <= 1.0, "flamed_den_solve_rk2_lens: stage parameter a = %g outside (0, 1]", a);
+  const Rk2 rk(a, nsteps);
+  return den_solve_lens(h, xt, mods, lens, 2 * nsteps, B, T, ws, ws_bytes, use_graph, &rk, st, "flamed_den_solve_rk2_lens");
 }
 
 }  // extern "C"

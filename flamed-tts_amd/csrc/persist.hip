@@ -67,18 +67,23 @@ __device__ __forceinline__ int opq(int v) {
 // Several utterances (B = 2, 4 or 8, each of T frames; rows u T .. u T + T - 1): utterance u owns the 8 / B
 // groups u 8/B .. + 8/B - 1 and splits its frames among them the same way, so a group never spans two
 // utterances (its modulation row, GroupNorm statistics and zero padding are its utterance's).
-__device__ __forceinline__ void group_rows(int g, int T, int B, int& r0, int& nr, int opt) {
+// Exact lengths (the ragged variants): the utterance's rows still start at u T, but it holds Lu <= T frames and its
+// groups split those (Lu = T is the dense split).
+__device__ __forceinline__ void group_rows(int g, int T, int Lu, int B, int& r0, int& nr, int opt) {
   const int gpu = kGroups / B, u = g / gpu, gi = g - u * gpu;
   if (opt & 2) {  // whole 16-row tiles [gi MT / gpu, (gi + 1) MT / gpu) of the utterance
-    const int MT = (T + 15) >> 4;
+    const int MT = (Lu + 15) >> 4;
     const int tb = gi * MT / gpu, te = (gi + 1) * MT / gpu;
     r0 = u * T + 16 * tb;
-    nr = max(min(16 * te, T) - 16 * tb, 0);
+    nr = max(min(16 * te, Lu) - 16 * tb, 0);
     return;
   }
-  const int R = (T + gpu - 1) / gpu;
+  const int R = (Lu + gpu - 1) / gpu;
   r0 = u * T + gi * R;
-  nr = max(min(R, T - gi * R), 0);
+  nr = max(min(R, Lu - gi * R), 0);
+}
+__device__ __forceinline__ void group_rows(int g, int T, int B, int& r0, int& nr, int opt) {
+  group_rows(g, T, T, B, r0, nr, opt);
 }
 
 // ---- hand-off primitives ----
@@ -812,7 +817,11 @@ __device__ __forceinline__ float2 gn_finalize(const float (&nv)[kGroups], const 
 // RK2: the two-stage second-order update (Params::rk2) with a base copy of the state, in registers up to two chunks
 // and in a thread-private global stash beyond (kStash below); the Euler variants (RK2 = false) compile exactly the
 // code they had before it existed.
-template <bool KH, int NTW, bool RK2 = false>
+// RAG: exact lengths (Params::lens): utterance u's row groups, GroupNorm count and zero padding follow lens[u] instead
+// of T, and the rows behind it are never touched.  A template parameter, so the dense variants compile the code they
+// had; instantiated for the chunk-count variants only (a multi-utterance launch reaches every one of them, Euler and
+// RK2, but never the 2 x 2 wave-split variant, which the host keeps dense).
+template <bool KH, int NTW, bool RK2 = false, bool RAG = false>
 __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -838,10 +847,16 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
   // 2 x 2 wave-split variant keeps the LDS table (with the eight loads held across gemm_kh it spills)
   constexpr bool kDefer = NTW == 1 && !KH;
   const bool gran = (P.opt & 512) != 0;       // GroupNorm partials as tagged granules (gnp zeroed per launch)
-  int r0, nr;
-  group_rows(g, T, P.B, r0, nr, P.opt);
   const int gpu = kGroups / P.B, utt = g / gpu;  // this group's utterance and its frames [ub, ue)
-  const int ub = utt * T, ue = ub + T;
+  // frames of group k's utterance (exact lengths: its own count; rows [ue, ub + T) then belong to nobody)
+  auto len_of = [&](int k) {
+    if constexpr (RAG) return P.lens[k / gpu];
+    else return T;
+  };
+  const int Tu = len_of(g);
+  int r0, nr;
+  group_rows(g, T, Tu, P.B, r0, nr, P.opt);
+  const int ub = utt * T, ue = ub + Tu;
   // padded batch (P.Bx): an idle utterance runs the same phases on zeros (every group still takes part in every
   // hand-off), without touching xt; its modulation row is the last real utterance's
   const bool idle = P.Bx > 0 && utt >= P.Bx;
@@ -1084,7 +1099,7 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
   int gp = 0, gn_ = 0;
   for (int k = 0; k < kGroups; ++k) {
     int a, b;
-    group_rows(k, T, P.B, a, b, P.opt);
+    group_rows(k, T, len_of(k), P.B, a, b, P.opt);
     if (b > 0 && a + b == r0) gp = k;
     if (b > 0 && a == r0 + nr) gn_ = k;
   }
@@ -1386,13 +1401,13 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
 #pragma unroll
             for (int k = 0; k < kGroups; ++k) {
               int ka, kn;
-              group_rows(k, T, P.B, ka, kn, P.opt);
+              group_rows(k, T, len_of(k), P.B, ka, kn, P.opt);
               nv[k] = (float)kn;
               GND(3 * k, nv[k]);
               GND(3 * k + 1, mv[k]);
               GND(3 * k + 2, qv[k]);
             }
-            const float2 ms = gn_finalize(nv, mv, qv, utt, gpu, T, gwv);
+            const float2 ms = gn_finalize(nv, mv, qv, utt, gpu, Tu, gwv);
             GND(24, ms.x);
             GND(25, ms.y);
             gnv[tid] = make_float4(ms.x, ms.y, gbv, 0.f);
@@ -1419,7 +1434,7 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
           GND(3 * k + 1, v.y);
           GND(3 * k + 2, v.z);
         }
-        const float2 ms = gn_finalize(nv, mv, qv, utt, gpu, T, gwv);
+        const float2 ms = gn_finalize(nv, mv, qv, utt, gpu, Tu, gwv);
         GND(24, ms.x);
         GND(25, ms.y);
         gnv[tid] = make_float4(ms.x, ms.y, gbv, 0.f);
@@ -1810,6 +1825,24 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
   }
 }
 
+#ifdef FL_PERSIST_RAGGED_TU
+// persist_rag.hip: this file once more, for the exact-lengths variants alone (a translation unit of their own, so the
+// two sets of kernels compile side by side): [ntw - 1] ntw chunks per group, the RK2 variants in the same order.
+template <bool RK2>
+static const void* persist_ragged_of(int ntw) {
+  static const void* const k[kMaxNTW] = {
+      reinterpret_cast<const void*>(den_persist_kernel<false, 1, RK2, true>), reinterpret_cast<const void*>(den_persist_kernel<false, 2, RK2, true>),
+      reinterpret_cast<const void*>(den_persist_kernel<false, 3, RK2, true>), reinterpret_cast<const void*>(den_persist_kernel<false, 4, RK2, true>),
+      reinterpret_cast<const void*>(den_persist_kernel<false, 5, RK2, true>), reinterpret_cast<const void*>(den_persist_kernel<false, 6, RK2, true>),
+      reinterpret_cast<const void*>(den_persist_kernel<false, 7, RK2, true>), reinterpret_cast<const void*>(den_persist_kernel<false, 8, RK2, true>)};
+  static_assert(kMaxNTW == 8, "kernel table");
+  return k[ntw - 1];
+}
+const void* persist_ragged_kernel(int ntw, bool rk2) { return rk2 ? persist_ragged_of<true>(ntw) : persist_ragged_of<false>(ntw); }
+
+}  // namespace pk
+}  // namespace fl
+#else
 #ifdef FL_STAMPS
 static unsigned long long* g_pst_buf = nullptr;
 static int g_pst_step = -1;
@@ -1842,6 +1875,7 @@ static const void* persist_kernel_of(int i) {
   return k[i];
 }
 static const void* persist_kernel(int i, bool rk2) { return rk2 ? persist_kernel_of<true>(i) : persist_kernel_of<false>(i); }
+const void* persist_ragged_kernel(int ntw, bool rk2);  // persist_rag.hip: ntw in 1..kMaxNTW
 
 bool persist_device_ok(int device) {
   int cus = 0, nb = 0;
@@ -1851,10 +1885,15 @@ bool persist_device_ok(int device) {
     if (set_max_lds(k) != hipSuccess) return false;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kThreads, kLds) != hipSuccess || nb < 1) return false;
   }
+  for (int i = 0; i < 2 * kMaxNTW; ++i) {  // the exact-lengths variants
+    const void* k = persist_ragged_kernel(1 + i % kMaxNTW, i >= kMaxNTW);
+    if (set_max_lds(k) != hipSuccess) return false;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kThreads, kLds) != hipSuccess || nb < 1) return false;
+  }
   return true;
 }
 
-int persist_launch(const Params& Pin, hipStream_t st, bool cooperative) {
+int persist_launch(const Params& Pin, hipStream_t st, bool cooperative, bool ragged) {
   Params P = Pin;
 #ifdef FL_STAMPS
   P.pst = g_pst_buf;
@@ -1874,7 +1913,19 @@ int persist_launch(const Params& Pin, hipStream_t st, bool cooperative) {
     set_error("persistent solve: a two-stage solver runs whole steps (evaluations [%d, %d))", P.s0, P.s1);
     return kBadArg;
   }
-  const void* kern = persist_kernel((P.opt & 1024) ? 0 : P.ntw, P.rk2 != 0);
+  if (ragged) {
+    if (P.B < 2 || (P.opt & 1024)) {
+      set_error("persistent solve: exact lengths take several utterances and no wave-split GEMM variant");
+      return kBadArg;
+    }
+    // every group's rows inside the batch's B x T rows, whatever the caller passed (the kernel trusts lens)
+    for (int u = 0; u < P.B; ++u)
+      if (P.lens[u] < 1 || P.lens[u] > P.T) {
+        set_error("persistent solve: utterance %d holds %d frames (1..%d)", u, P.lens[u], P.T);
+        return kBadArg;
+      }
+  }
+  const void* kern = ragged ? persist_ragged_kernel(P.ntw, P.rk2 != 0) : persist_kernel((P.opt & 1024) ? 0 : P.ntw, P.rk2 != 0);
   // tune coop 0: plain launch (profiling: rocprofv3's teardown faults after cooperative launches, README);
   // residency was checked by persist_eligible either way
   const hipError_t e = cooperative && tn().coop ? hipLaunchCooperativeKernel(kern, dim3(kWGs), dim3(kThreads), args, kLds, st)
@@ -1902,3 +1953,4 @@ extern "C" FLAMED_API int flamed_persist_ticket(unsigned ticket, unsigned cur, u
   *reached = fl::pk::arrive_reached(cur, *target) ? 1 : 0;
   return fl::kOk;
 }
+#endif  // FL_PERSIST_RAGGED_TU

@@ -139,9 +139,14 @@ struct Params {
   float* xbase = nullptr;  // the step's base x of the variants with >= 3 chunks per group (B T x C, thread-private
                            // elements: each thread stores and reloads its own)
   // The depthwise taps of block i once more, channel-major: (H, 32) fp32 with tap 31 zero, which a thread reads as
-  // eight 16-B loads (the kernel variants up to four chunks per group; the others read blk[i].dww).  Last in the
-  // struct: the variants that do not read it see the kernel arguments they always had.
+  // eight 16-B loads (the kernel variants up to four chunks per group; the others read blk[i].dww).  Behind every
+  // older field: the variants that do not read it see the kernel arguments they always had.
   const float* dwc[kMaxNB + 1] = {};
+  // Exact lengths (the ragged kernel variants only; appended, so every field above keeps its offset): utterance u
+  // holds lens[u] <= T frames at rows u T .. u T + lens[u] - 1 and is solved over those alone -- its row groups split
+  // lens[u], its GroupNorm divides by it, its zero padding sits at its own end, and rows u T + lens[u] .. (u + 1) T - 1
+  // of xt and of every scratch image are neither read nor written.  Idle utterances (Bx) carry T.
+  int lens[kGroups] = {};
 };
 
 // Host side (persist.hip): whether this device runs the 256-workgroup grid fully resident, and the launch.
@@ -153,7 +158,8 @@ inline int persist_ntw(int B, int T, int opt) {
   if (opt & 2) R = ((T + 15) / 16 + gpu - 1) / gpu * 16;
   return (R + kChunk - 1) / kChunk;
 }
-int persist_launch(const Params& P, hipStream_t st, bool cooperative = true);
+// ragged: the exact-lengths variants (Params::lens; several utterances only).
+int persist_launch(const Params& P, hipStream_t st, bool cooperative = true, bool ragged = false);
 
 }  // namespace pk
 }  // namespace fl

@@ -37,6 +37,9 @@ SIGNATURES = {
     "flamed_den_step": (c_int, [P, P, P, c_int, c_int, c_int, c_float, P, c_size_t, P]),
     "flamed_den_solve": (c_int, [P, P, P, c_int, c_int, c_int, P, c_size_t, c_int, P]),
     "flamed_den_solve_rk2": (c_int, [P, P, P, c_int, ctypes.c_double, c_int, c_int, P, c_size_t, c_int, P]),
+    "flamed_den_solve_lens": (c_int, [P, P, P, ctypes.POINTER(c_int), c_int, c_int, c_int, P, c_size_t, c_int, P]),
+    "flamed_den_solve_rk2_lens": (c_int, [P, P, P, ctypes.POINTER(c_int), c_int, ctypes.c_double, c_int, c_int, P, c_size_t,
+                                          c_int, P]),
     "flamed_den_solve_chunk": (c_int, [P, c_int]),
     "flamed_den_persist_info": (c_int, [P, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_float)]),
     "flamed_den_persist_times": (c_int, [P, ctypes.POINTER(c_float), c_int]),
@@ -53,6 +56,7 @@ SIGNATURES = {
     "flamed_cond_load": (c_int, [P, ctypes.POINTER(P), c_int, P]),
     "flamed_cond_workspace_size": (c_size_t, [P, c_int, c_int]),
     "flamed_cond_fold": (c_int, [P, P, P, c_int, c_int, P, P, c_size_t, P]),
+    "flamed_cond_fold_exact": (c_int, [P, P, P, c_int, c_int, P, P, c_size_t, P]),
     "flamed_dur_create": (c_int, [c_int, c_int, c_int, ctypes.POINTER(P)]),
     "flamed_dur_destroy": (c_int, [P]),
     "flamed_dur_load": (c_int, [P, ctypes.POINTER(P), c_int, P]),

@@ -72,10 +72,11 @@ class Flamed(nn.Module):
                timbre: torch.Tensor = None, sr: int = 16000, codec_cfg=None, codec_encoder=None, codec_decoder=None,
                temp_durgen: float = 0.3, temp_denoiser: float = 0.3, nsteps_durgen: int = 64,
                nsteps_denoiser: int = 64, lexicon_path: str = None, cleaners=("english_cleaners",),
-               solver_denoiser: str = "euler"):
+               solver_denoiser: str = "euler", exact_lengths: bool = False):
         """reference :89-166 (same argument validation and ValueErrors).  solver_denoiser: the denoiser's ODE
         solver ("euler", the reference's; "midpoint" / "heun": second order, nsteps_denoiser then counts velocity
-        evaluations and must be even -- ProbGenerator.sample)."""
+        evaluations and must be even -- ProbGenerator.sample).  exact_lengths: as in sample_batch (one utterance has
+        no padding, so it changes nothing here)."""
         if codec_decoder is None or (codec_encoder is None and prompt_raw is not None):
             if codec_cfg is None:
                 raise ValueError("The codec_encoder or codec_decoder is set to None. To initialize the codec encoder or "
@@ -111,15 +112,18 @@ class Flamed(nn.Module):
                                                     device=self.device),
                                 prompts=prompts, timbres=timbre, codec_decoder=codec_decoder, temp_durgen=temp_durgen,
                                 temp_denoiser=temp_denoiser, nsteps_durgen=nsteps_durgen,
-                                nsteps_denoiser=nsteps_denoiser, solver_denoiser=solver_denoiser)
+                                nsteps_denoiser=nsteps_denoiser, solver_denoiser=solver_denoiser,
+                                exact_lengths=exact_lengths)
         wav = out["wav"][0][0].detach().cpu().numpy()
         return {"wav": wav, "time": time.time() - start}
 
     @torch.inference_mode()
     def sample_batch(self, phonemes, src_lens, prompts, timbres, codec_decoder=None, temp_durgen: float = 0.3,
                      temp_denoiser: float = 0.3, nsteps_durgen: int = 64, nsteps_denoiser: int = 64,
-                     solver_denoiser: str = "euler"):
-        """reference :168-217; solver_denoiser as in sample"""
+                     solver_denoiser: str = "euler", exact_lengths: bool = False):
+        """reference :168-217; solver_denoiser as in sample.  exact_lengths (opt-in): every utterance of the padded
+        batch gets the latents it would get alone -- its condition fold and its solve run over its own frames only
+        and its padding frames are 0 (ProbGenerator.sample); the FaCodec decode is unchanged."""
         start = time.time()
         dev = self.device
         phonemes, src_lens, prompts, timbres = phonemes.to(dev), src_lens.to(dev), prompts.to(dev), timbres.to(dev)
@@ -128,7 +132,7 @@ class Flamed(nn.Module):
             prompts_len=prompts.size(-1), nfe=nsteps_durgen, temperature=temp_durgen)
         latents = self.prob_generator.sample(cond=prior_emb_cond, spk=timbres, nfe=nsteps_denoiser,
                                              temperature=temp_denoiser, mask=~tgt_mask.unsqueeze(-1),
-                                             solver=solver_denoiser)
+                                             solver=solver_denoiser, exact_lengths=exact_lengths)
         if latents.is_cuda:
             torch.cuda.synchronize(latents.device)  # 'time' covers the device work, as the eager reference does
             den = self.prob_generator.denoiser

@@ -271,6 +271,22 @@ class SimpleMLPAdaLN(nn.Module):
         return self.final_layer(h, y)
 
 
+def prefix_lengths(mask) -> List[int]:
+    """Frames per utterance of a prefix mask (B, T, 1) / (B, T), True = valid (one host copy); anything that is not
+    `arange(T) < len` with len >= 1 raises ValueError."""
+    m = mask.reshape(mask.shape[0], -1).ne(0).cpu()
+    lens = m.sum(dim=1)
+    if not bool((m == (torch.arange(m.shape[1])[None, :] < lens[:, None])).all()) or int(lens.min()) < 1:
+        raise ValueError("exact lengths need a prefix mask (arange(T) < len, len >= 1) for every utterance")
+    return [int(n) for n in lens]
+
+
+def check_groupnorm_frames(B: int, T: int, channels: int):
+    """The reference's GroupNorm(H, H) over T (F.group_norm's batch-size check) rejects a single value per channel."""
+    if B * T == 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {[1, channels, 1]}")
+
+
 class ProbGenerator(nn.Module):
     """Condition fold + flow-matching Euler sampler over SimpleMLPAdaLN (reference :384-447)."""
 
@@ -304,14 +320,26 @@ class ProbGenerator(nn.Module):
         q, d = self.quantizer_encoding.quantizer_emb.weight.shape
         return nat.supported("cond", q, d, self.target_dim, self.n_stages, nat.dtype_code(self.cond_hip_dtype))
 
-    def fold_condition(self, cond, mask):
+    def fold_condition(self, cond, mask, exact=False):
         """QuantizerEncoding + ConditionDownSampler (reference :435-436); on ROCm at inference one HIP
         call (flamed_cond_fold: three GEMMs with the quantizer encoding, GroupNorm/Mish/residual and
-        GroupNorm/ReLU applied in their operand loaders)."""
+        GroupNorm/ReLU applied in their operand loaders).
+
+        exact: every utterance is folded over its own frames only (mask a prefix mask): what it gets alone at
+        T = its length with a mask of ones, and 0 on its padding frames (flamed_cond_fold_exact)."""
         if self._cond_hip_ok(cond):
             if self._cond_hip is None or self._cond_hip.dtype_name != self.cond_hip_dtype:
                 self._cond_hip = CondFoldHIP(self, self.cond_hip_dtype)
+            if exact:
+                return ops.cond_fold_exact(self._cond_hip.oid, cond, mask)
             return ops.cond_fold(self._cond_hip.oid, cond, mask)
+        if exact:
+            outs = []
+            for u, n in enumerate(prefix_lengths(mask)):
+                ones = torch.ones((1, n, 1), dtype=torch.bool, device=cond.device)
+                f = self.cond_downsampling(self.quantizer_encoding(cond[u:u + 1, :, :n]), ones)
+                outs.append(F.pad(f, (0, 0, 0, cond.shape[2] - n)))
+            return torch.cat(outs, dim=0)
         return self.cond_downsampling(self.quantizer_encoding(cond), mask)
 
     def _load_from_state_dict(self, *args, **kwargs):
@@ -331,9 +359,14 @@ class ProbGenerator(nn.Module):
         x1_est = (xt + (1 - k * t) * vt) * mask
         return {"fm_loss": F.mse_loss(vt, dx), "anchor_loss": F.mse_loss(x1_est, x1)}
 
-    def sample(self, cond, spk, mask, nfe=4, temperature=1.0, solver="euler"):
+    def sample(self, cond, spk, mask, nfe=4, temperature=1.0, solver="euler", exact_lengths=False):
         """reference :434-447.  Noise is drawn from the global CPU RNG with the reference's shape and
         order, so seeded runs reproduce the reference trajectory.
+
+        exact_lengths (opt-in; the default is the reference's padded batch, bit for bit): utterance u of the padded
+        batch, len_u frames by its (prefix) mask, is folded and solved over those frames alone -- exactly what it gets
+        alone at T = len_u from noise[u, :len_u] of the same (B, T, C) draw -- and its padding frames come out 0.  So an
+        utterance's latents no longer depend on which others share its batch.
 
         solver: "euler" (the reference's loop, the default), or a two-stage second-order method, "midpoint"
         (a = 1/2) or "heun" (a = 1).  nfe always counts velocity evaluations, so a second-order solver takes
@@ -345,32 +378,60 @@ class ProbGenerator(nn.Module):
         a = SOLVERS[solver]
         if a is not None and (nfe < 2 or nfe % 2):
             raise ValueError(f"solver {solver!r} takes two velocity evaluations per step: nfe must be even, got {nfe}")
-        cond = self.fold_condition(cond, mask)
+        lens = None
+        if exact_lengths:
+            lens = prefix_lengths(mask)
+            for n in lens:
+                check_groupnorm_frames(1, n, self.denoiser.model_channels)
+        cond = self.fold_condition(cond, mask, exact=True) if exact_lengths else self.fold_condition(cond, mask)
         b, l, _ = cond.shape
         xt = torch.randn((b, l, self.target_dim)).to(cond.device) * temperature + cond
         if a is None:
             ts = torch.linspace(0, 1, nfe + 1, device=cond.device)
             if self.denoiser._use_hip(xt):
+                if lens is not None:
+                    return ops.den_solve_lens(self.denoiser.hip().oid, xt, ts, spk, nfe, lens).transpose(1, -1)
                 xt = ops.den_solve(self.denoiser.hip().oid, xt, ts, spk, nfe)
+            elif lens is not None:
+                xt = self._each_alone(xt, spk, lens, lambda x, c: self._euler_torch(x, ts, c, nfe))
             else:
-                delta_t = 1 / nfe
-                for i in range(1, len(ts)):
-                    xt = xt + delta_t * self.denoiser(xt, ts[i - 1].unsqueeze(0).unsqueeze(1), spk)
+                xt = self._euler_torch(xt, ts, spk, nfe)
             return xt.transpose(1, -1)
         nsteps = nfe // 2
         ts = torch.linspace(0, 1, nsteps + 1, device=cond.device)
         delta_t = 1 / nsteps
-        c1, c2 = (2 * a - 1) / (2 * a * a), 1 / (2 * a)
         if self.denoiser._use_hip(xt):
             # evaluation times [t_0, t_0 + a dt, t_1, t_1 + a dt, ...]: one modulation row block per evaluation
             ts_eval = torch.stack((ts[:-1], ts[:-1] + a * delta_t), dim=1).reshape(-1)
+            if lens is not None:
+                return ops.den_solve_rk2_lens(self.denoiser.hip().oid, xt, ts_eval, spk, nsteps, a, lens).transpose(1, -1)
             xt = ops.den_solve_rk2(self.denoiser.hip().oid, xt, ts_eval, spk, nsteps, a)
+        elif lens is not None:
+            xt = self._each_alone(xt, spk, lens, lambda x, c: self._rk2_torch(x, ts, c, nsteps, a))
         else:
-            for i in range(nsteps):
-                y = xt + (a * delta_t) * self.denoiser(xt, ts[i].unsqueeze(0).unsqueeze(1), spk)
-                v = self.denoiser(y, (ts[i] + a * delta_t).unsqueeze(0).unsqueeze(1), spk)
-                xt = (xt + c1 * (y - xt) if c1 else xt) + (c2 * delta_t) * v
+            xt = self._rk2_torch(xt, ts, spk, nsteps, a)
         return xt.transpose(1, -1)
+
+    def _euler_torch(self, xt, ts, spk, nfe):
+        delta_t = 1 / nfe
+        for i in range(1, len(ts)):
+            xt = xt + delta_t * self.denoiser(xt, ts[i - 1].unsqueeze(0).unsqueeze(1), spk)
+        return xt
+
+    def _rk2_torch(self, xt, ts, spk, nsteps, a):
+        delta_t = 1 / nsteps
+        c1, c2 = (2 * a - 1) / (2 * a * a), 1 / (2 * a)
+        for i in range(nsteps):
+            y = xt + (a * delta_t) * self.denoiser(xt, ts[i].unsqueeze(0).unsqueeze(1), spk)
+            v = self.denoiser(y, (ts[i] + a * delta_t).unsqueeze(0).unsqueeze(1), spk)
+            xt = (xt + c1 * (y - xt) if c1 else xt) + (c2 * delta_t) * v
+        return xt
+
+    @staticmethod
+    def _each_alone(xt, spk, lens, solve):
+        """Exact lengths on torch ops: utterance u's first lens[u] frames solved alone, 0 behind them."""
+        outs = [F.pad(solve(xt[u:u + 1, :n], spk[u:u + 1]), (0, 0, 0, xt.shape[1] - n)) for u, n in enumerate(lens)]
+        return torch.cat(outs, dim=0)
 
 
 # ------------------------------------------------------------------ HIP backend
@@ -412,8 +473,9 @@ class DenoiserHIP:
         # on the graph of launches into the same output tensor, so a failure never survives to the caller's
         # host copy; skipped inside a stream capture (the caller then owns the check: persist_status)
         self.check_persist = True
-        # (launch seq, output, input x, ts, spk, nfe, a) of solves not yet known to have succeeded (a: the stage
-        # parameter of a two-stage solve, None for Euler; nfe counts velocity evaluations either way)
+        # (launch seq, output, input x, ts, spk, nfe, a, lens) of solves not yet known to have succeeded (a: the stage
+        # parameter of a two-stage solve, None for Euler; nfe counts velocity evaluations either way; lens: the
+        # lengths of an exact-lengths solve, None otherwise)
         self._pending = []
         self.oid = ops.register(self)  # torch.ops.flamed_hip.den_* carry this id
 
@@ -473,9 +535,7 @@ class DenoiserHIP:
     def _check_groupnorm(self, B: int, T: int):
         """The reference's GroupNorm(H, H) over T (F.group_norm's batch-size check) rejects a single
         value per channel; the HIP path raises the same ValueError instead of normalising it."""
-        if B * T == 1:
-            raise ValueError(f"Expected more than 1 value per channel when training, got input size "
-                             f"{[1, self.den.model_channels, 1]}")
+        check_groupnorm_frames(B, T, self.den.model_channels)
 
     def velocity(self, x: torch.Tensor, t: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
         dev = x.device
@@ -530,37 +590,58 @@ class DenoiserHIP:
             nat.check(-1, "flamed_den_persist_times")
         return [float(buf[i]) for i in range(k)]
 
-    def solve(self, xt: torch.Tensor, ts: torch.Tensor, spk: torch.Tensor, nfe: int) -> torch.Tensor:
+    def solve(self, xt: torch.Tensor, ts: torch.Tensor, spk: torch.Tensor, nfe: int, lens=None) -> torch.Tensor:
         """Full Euler solve; returns a new (B,T,C) fp32 tensor.  Only enqueues work: a persistent launch is
-        checked later (settle), and a failed one re-written in place before the caller's next sync point."""
-        return self._solve(xt, ts, spk, nfe, None)
+        checked later (settle), and a failed one re-written in place before the caller's next sync point.
 
-    def solve_rk2(self, xt: torch.Tensor, ts_eval: torch.Tensor, spk: torch.Tensor, nsteps: int, a: float) -> torch.Tensor:
+        lens (B ints, 2 <= lens[u] <= T): exact lengths (flamed_den_solve_lens) -- utterance u is solved over
+        xt[u, :lens[u]] alone, the frames behind it are never read (they may hold anything) and come out 0."""
+        return self._solve(xt, ts, spk, nfe, None, lens)
+
+    def solve_rk2(self, xt: torch.Tensor, ts_eval: torch.Tensor, spk: torch.Tensor, nsteps: int, a: float,
+                  lens=None) -> torch.Tensor:
         """Full solve with the two-stage second-order method of stage parameter a (0.5 midpoint, 1 Heun):
         nsteps steps, ts_eval the 2 nsteps evaluation times [t_0, t_0 + a dt, t_1, t_1 + a dt, ...]
-        (flamed_den_solve_rk2).  Same contract as solve, and a failed persistent launch is re-run as RK2."""
+        (flamed_den_solve_rk2).  Same contract as solve (lens included), and a failed persistent launch is re-run
+        as RK2."""
         nsteps, a = int(nsteps), float(a)
         if nsteps < 1 or not 0.0 < a <= 1.0:
             raise ValueError(f"solve_rk2: nsteps >= 1 and 0 < a <= 1 required; got nsteps = {nsteps}, a = {a}")
         if ts_eval.numel() < 2 * nsteps:
             raise ValueError(f"solve_rk2: {2 * nsteps} evaluation times required, got {ts_eval.numel()}")
-        return self._solve(xt, ts_eval, spk, 2 * nsteps, a)
+        return self._solve(xt, ts_eval, spk, 2 * nsteps, a, lens)
 
-    def _solve(self, xt, ts, spk, nfe, a):
+    @staticmethod
+    def _zero_padding(x, lens):
+        """x with the frames behind each utterance's length set to 0: a select, so NaN there never survives (and the
+        NaN poison of a failed launch on the valid frames does)."""
+        valid = torch.arange(x.shape[1], device=x.device)[None, :] < torch.tensor(lens, device=x.device)[:, None]
+        return torch.where(valid[:, :, None], x, torch.zeros((), dtype=x.dtype, device=x.device))
+
+    def _solve(self, xt, ts, spk, nfe, a, lens=None):
         dev = xt.device
         self._ensure(dev)
         B, T, C = xt.shape
         self._check_groupnorm(B, T)
+        if lens is not None:
+            lens = [int(n) for n in lens]
+            if len(lens) != B:
+                raise ValueError(f"lens: {B} lengths required, got {len(lens)}")
+            for n in lens:
+                self._check_groupnorm(1, n)
+                if not 2 <= n <= T:
+                    raise ValueError(f"lens: every length must lie in 2..T = {T}, got {lens}")
         capturing = torch.cuda.is_current_stream_capturing()
         if self._pending and not capturing:  # (event queries are not allowed while a stream captures)
             self.settle(block=False)
         runs0, _ = self.persist_status()
-        x = self._launch(xt, ts, spk, nfe, 0, a)
-        out = x.clone()
+        x = self._launch(xt, ts, spk, nfe, 0, a, lens)
+        out = x.clone() if lens is None else self._zero_padding(x, lens)
         if self.check_persist and not capturing and self.persist_status()[0] > runs0:
             seq = ctypes.c_longlong(-1)
             nat.check(nat.lib().flamed_den_persist_last(self.handle, ctypes.byref(seq)), "flamed_den_persist_last")
-            self._pending.append((seq.value, out, xt.detach().clone(), ts.detach().clone(), spk.detach().clone(), nfe, a))
+            self._pending.append((seq.value, out, xt.detach().clone(), ts.detach().clone(), spk.detach().clone(), nfe, a,
+                                  lens))
             if len(self._pending) > 32:  # the launch ring holds 64: settle the oldest before their slots are reused
                 self.settle(block=True)
         return out
@@ -578,7 +659,7 @@ class DenoiserHIP:
             torch.cuda.synchronize(self._pending[0][1].device)
         keep, reruns = [], 0
         for rec in self._pending:
-            seq, out, x0, ts, spk, nfe, a = rec
+            seq, out, x0, ts, spk, nfe, a, lens = rec
             st = ctypes.c_int(0)
             nat.check(L.flamed_den_persist_query(self.handle, seq, ctypes.byref(st)), "flamed_den_persist_query")
             state = st.value
@@ -590,14 +671,16 @@ class DenoiserHIP:
             if state == 1:
                 warnings.warn("flamed: persistent solve failed (its output was NaN-poisoned); "
                               "re-running it on the graph of launches")
-                out.copy_(self._launch(x0, ts, spk, nfe, 2, a))  # with the solver of the failed launch
+                x = self._launch(x0, ts, spk, nfe, 2, a, lens)  # with the solver (and lengths) of the failed launch
+                out.copy_(x if lens is None else self._zero_padding(x, lens))
                 reruns += 1
         self._pending = keep
         return reruns
 
-    def _launch(self, xt, ts, spk, nfe, extra_graph_bits, a=None):
+    def _launch(self, xt, ts, spk, nfe, extra_graph_bits, a=None, lens=None):
         """AdaLN rows + flamed_den_solve (a None) or flamed_den_solve_rk2 (stage parameter a) into the handle's
-        solve buffer (returned, not copied); nfe velocity evaluations at the times ts[:nfe]."""
+        solve buffer (returned, not copied); nfe velocity evaluations at the times ts[:nfe].  lens: the _lens
+        entry points (the buffer's frames behind each length keep whatever xt held)."""
         dev = xt.device
         B, T, C = xt.shape
         L = nat.lib()
@@ -608,7 +691,10 @@ class DenoiserHIP:
             bufs = {"x": torch.empty((B, T, C), dtype=torch.float32, device=dev),
                     "tidx": (r // B).to(torch.int32), "sidx": (r % B).to(torch.int32)}
             self._solve_bufs = {key: bufs}
-        ws = self.ws.get(L.flamed_den_workspace_size(self.handle, B, T), dev)
+        nbytes = L.flamed_den_workspace_size(self.handle, B, T)
+        if lens is not None:  # (an ineligible batch solves one utterance after another in the same workspace)
+            nbytes = max([nbytes] + [L.flamed_den_workspace_size(self.handle, 1, n) for n in set(lens)])
+        ws = self.ws.get(nbytes, dev)
         if "mods" not in bufs:
             bufs["mods"] = torch.empty((nfe * B, L.flamed_den_mods_stride(self.handle)), dtype=torch.float32, device=dev)
         # AdaLN rows of every step first (computing the later rows on a side stream while the first graph
@@ -616,6 +702,18 @@ class DenoiserHIP:
         self.adaln(ts[:nfe], spk, bufs["tidx"], bufs["sidx"], out=bufs["mods"])
         bufs["x"].copy_(xt)
         use_graph = int(bool(self.den.hip_graph)) | extra_graph_bits
+        if lens is not None:
+            cl = (ctypes.c_int * B)(*lens)
+            rerun = " (re-run)" if extra_graph_bits else ""
+            if a is not None:
+                nat.check(L.flamed_den_solve_rk2_lens(self.handle, nat.ptr(bufs["x"]), nat.ptr(bufs["mods"]), cl, nfe // 2, a,
+                                                      B, T, nat.ptr(ws), ws.numel(), use_graph, nat.stream_ptr(dev)),
+                          "flamed_den_solve_rk2_lens" + rerun)
+            else:
+                nat.check(L.flamed_den_solve_lens(self.handle, nat.ptr(bufs["x"]), nat.ptr(bufs["mods"]), cl, nfe, B, T,
+                                                  nat.ptr(ws), ws.numel(), use_graph, nat.stream_ptr(dev)),
+                          "flamed_den_solve_lens" + rerun)
+            return bufs["x"]
         if a is not None:
             nat.check(L.flamed_den_solve_rk2(self.handle, nat.ptr(bufs["x"]), nat.ptr(bufs["mods"]), nfe // 2, a, B, T,
                                              nat.ptr(ws), ws.numel(), use_graph, nat.stream_ptr(dev)),
@@ -682,8 +780,9 @@ class CondFoldHIP:
         self._keep = keep
         self._sig = sig
 
-    def fold(self, cond: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
-        """cond (B, Q, T, D), mask (B, T, 1) True = valid -> (B, T, target_dim) fp32."""
+    def fold(self, cond: torch.Tensor, mask: torch.Tensor, exact: bool = False) -> torch.Tensor:
+        """cond (B, Q, T, D), mask (B, T, 1) True = valid -> (B, T, target_dim) fp32.  exact: GroupNorm statistics
+        over each utterance's valid frames only, 0 on the others (flamed_cond_fold_exact)."""
         dev = cond.device
         self._ensure(dev)
         B, Q, T, D = cond.shape
@@ -692,6 +791,7 @@ class CondFoldHIP:
         out = torch.empty((B, T, self.pg.target_dim), dtype=torch.float32, device=dev)
         L = nat.lib()
         ws = self.ws.get(L.flamed_cond_workspace_size(self.handle, B, T), dev)
-        nat.check(L.flamed_cond_fold(self.handle, nat.ptr(c), nat.ptr(m), B, T, nat.ptr(out), nat.ptr(ws), ws.numel(),
-                                     nat.stream_ptr(dev)), "flamed_cond_fold")
+        fn, name = (L.flamed_cond_fold_exact, "flamed_cond_fold_exact") if exact else (L.flamed_cond_fold, "flamed_cond_fold")
+        nat.check(fn(self.handle, nat.ptr(c), nat.ptr(m), B, T, nat.ptr(out), nat.ptr(ws), ws.numel(),
+                     nat.stream_ptr(dev)), name)
         return out

@@ -13,6 +13,9 @@ take tensors and scalars only); the registry holds weak references, so a dropped
   flamed_hip::den_solve(id, xt, ts, spk, nfe)      ProbGenerator.sample Euler loop prob_generator.py:439-445
   flamed_hip::den_solve_rk2(id, xt, ts_eval, spk, nsteps, a)  the same loop, two-stage second-order solver
   flamed_hip::cond_fold(id, cond, mask)            QuantizerEncoding + ConditionDownSampler :167-205, 435-436
+  flamed_hip::den_solve_lens(id, xt, ts, spk, nfe, lens)            exact lengths (no reference counterpart): every
+  flamed_hip::den_solve_rk2_lens(id, xt, ts_eval, spk, nsteps, a, lens)  utterance of the padded batch solved / folded
+  flamed_hip::cond_fold_exact(id, cond, mask)                       over its own frames only, as if alone
   flamed_hip::pva_flow(id, x, mask, dur, sil, ts, nfe)  PVA.sample Euler loops       pva.py:97-109
   flamed_hip::length_regulate(x, pd, sd, lens, max_len, log_domain)  LengthRegulator.LR  pva.py:125-166
   flamed_hip::fac_decode(id, x, spk)               FACodecDecoder.inference        facodec.py:630-638
@@ -30,7 +33,7 @@ from __future__ import annotations
 import itertools
 import threading
 import weakref
-from typing import Tuple
+from typing import List, Tuple
 
 import torch
 from torch import Tensor
@@ -87,12 +90,43 @@ def _(oid, xt, ts_eval, spk, nsteps, a):
     return xt.new_empty(xt.shape, dtype=torch.float32)
 
 
+@torch.library.custom_op("flamed_hip::den_solve_lens", mutates_args=())
+def den_solve_lens(oid: int, xt: Tensor, ts: Tensor, spk: Tensor, nfe: int, lens: List[int]) -> Tensor:
+    return owner(oid).solve(xt, ts, spk, nfe, lens=lens)
+
+
+@den_solve_lens.register_fake
+def _(oid, xt, ts, spk, nfe, lens):
+    return xt.new_empty(xt.shape, dtype=torch.float32)
+
+
+@torch.library.custom_op("flamed_hip::den_solve_rk2_lens", mutates_args=())
+def den_solve_rk2_lens(oid: int, xt: Tensor, ts_eval: Tensor, spk: Tensor, nsteps: int, a: float, lens: List[int]) -> Tensor:
+    return owner(oid).solve_rk2(xt, ts_eval, spk, nsteps, a, lens=lens)
+
+
+@den_solve_rk2_lens.register_fake
+def _(oid, xt, ts_eval, spk, nsteps, a, lens):
+    return xt.new_empty(xt.shape, dtype=torch.float32)
+
+
 @torch.library.custom_op("flamed_hip::cond_fold", mutates_args=())
 def cond_fold(oid: int, cond: Tensor, mask: Tensor) -> Tensor:
     return owner(oid).fold(cond, mask)
 
 
 @cond_fold.register_fake
+def _(oid, cond, mask):
+    B, _, T, _ = cond.shape
+    return cond.new_empty((B, T, owner(oid).pg.target_dim), dtype=torch.float32)
+
+
+@torch.library.custom_op("flamed_hip::cond_fold_exact", mutates_args=())
+def cond_fold_exact(oid: int, cond: Tensor, mask: Tensor) -> Tensor:
+    return owner(oid).fold(cond, mask, exact=True)
+
+
+@cond_fold_exact.register_fake
 def _(oid, cond, mask):
     B, _, T, _ = cond.shape
     return cond.new_empty((B, T, owner(oid).pg.target_dim), dtype=torch.float32)
@@ -191,5 +225,5 @@ def _(oid, x, tgt_mask, prompts, prompts_len):
     return x.new_empty((B, nq, T, D)), x.new_empty((B, V1, nq, T))
 
 
-OPS = ("den_velocity", "den_solve", "den_solve_rk2", "cond_fold", "pva_flow", "length_regulate", "fac_decode", "enc_encode",
-       "vq_encode", "prior_encode", "prior_decode")
+OPS = ("den_velocity", "den_solve", "den_solve_rk2", "den_solve_lens", "den_solve_rk2_lens", "cond_fold", "cond_fold_exact",
+       "pva_flow", "length_regulate", "fac_decode", "enc_encode", "vq_encode", "prior_encode", "prior_decode")

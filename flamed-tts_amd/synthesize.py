@@ -192,16 +192,16 @@ class RtfMeter:
         return sum(d * SR / HOP for d in self.durations) / total if total > 0 else float("nan")
 
 
-def _solver_suffix(solver_denoiser: str) -> str:
-    return "" if solver_denoiser == "euler" else f"-{solver_denoiser}"
+def _solver_suffix(solver_denoiser: str, exact_lengths: bool = False) -> str:
+    return ("" if solver_denoiser == "euler" else f"-{solver_denoiser}") + ("-exact" if exact_lengths else "")
 
 
 def synthesize_with_prompts(model: Flamed, codec_encoder, codec_decoder, text: str, prompt_dir: str,
                             prompt_list: List[str], output_dir: str, nsteps_durgen: int, nsteps_denoiser: int,
                             temp_durgen: float, temp_denoiser: float, meter: Optional[RtfMeter] = None,
-                            solver_denoiser: str = "euler"):
+                            solver_denoiser: str = "euler", exact_lengths: bool = False):
     """One `Flamed.sample` per prompt (reference :194-217).  A denoiser solver other than Euler is appended to the
-    output names, so runs with different solvers do not overwrite each other."""
+    output names, so runs with different solvers do not overwrite each other; so is `-exact` for exact lengths."""
     os.makedirs(output_dir, exist_ok=True)
     meter = meter if meter is not None else RtfMeter()
     rank, world, _ = fdist.dist_env()
@@ -209,10 +209,11 @@ def synthesize_with_prompts(model: Flamed, codec_encoder, codec_decoder, text: s
         audio_prompt = load_audio(_resolve_prompt_path(prompt_dir, prompt_name))
         res = model.sample(text=text, prompt_raw=audio_prompt, sr=SR, codec_encoder=codec_encoder,
                            codec_decoder=codec_decoder, nsteps_durgen=nsteps_durgen, nsteps_denoiser=nsteps_denoiser,
-                           temp_durgen=temp_durgen, temp_denoiser=temp_denoiser, solver_denoiser=solver_denoiser)
+                           temp_durgen=temp_durgen, temp_denoiser=temp_denoiser, solver_denoiser=solver_denoiser,
+                           exact_lengths=exact_lengths)
         meter.add(res["time"], len(res["wav"]))
         stem = os.path.splitext(os.path.basename(prompt_name))[0]
-        out_name = f"{stem}-{nsteps_durgen}-{nsteps_denoiser}-{temp_durgen}-{temp_denoiser}{_solver_suffix(solver_denoiser)}.wav"
+        out_name = f"{stem}-{nsteps_durgen}-{nsteps_denoiser}-{temp_durgen}-{temp_denoiser}{_solver_suffix(solver_denoiser, exact_lengths)}.wav"
         write_wav(os.path.join(output_dir, out_name), res["wav"], SR)
     return meter.rtf()
 
@@ -220,12 +221,14 @@ def synthesize_with_prompts(model: Flamed, codec_encoder, codec_decoder, text: s
 def synthesize_with_metadata(model: Flamed, codec_encoder, codec_decoder, metadata_file: str, prompt_dir: str,
                              output_dir: str, nsteps_durgen: int, nsteps_denoiser: int, temp_durgen: float,
                              temp_denoiser: float, skip_existing: bool, batch_size: int,
-                             meter: Optional[RtfMeter] = None, solver_denoiser: str = "euler"):
+                             meter: Optional[RtfMeter] = None, solver_denoiser: str = "euler",
+                             exact_lengths: bool = False):
     """Batched `Flamed.sample_batch` over a `target|prompt|text` file (reference :220-303).  A denoiser solver
-    other than Euler is appended to the target directory's name."""
+    other than Euler is appended to the target directory's name, and `-exact` for exact lengths (every utterance of
+    a padded batch then gets the latents it would get alone)."""
     with open(metadata_file, "r", encoding="utf-8") as fin:
         entries = [line.strip() for line in fin if line.strip()]
-    target_dir = os.path.join(output_dir, f"nfe{nsteps_denoiser}-temp{temp_denoiser}{_solver_suffix(solver_denoiser)}")
+    target_dir = os.path.join(output_dir, f"nfe{nsteps_denoiser}-temp{temp_denoiser}{_solver_suffix(solver_denoiser, exact_lengths)}")
     os.makedirs(target_dir, exist_ok=True)
     meter = meter if meter is not None else RtfMeter()
     cache: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
@@ -253,7 +256,7 @@ def synthesize_with_metadata(model: Flamed, codec_encoder, codec_decoder, metada
         out = model.sample_batch(phonemes=phonemes, src_lens=src_lens, prompts=prompts, timbres=timbres,
                                  codec_decoder=codec_decoder, temp_durgen=temp_durgen, temp_denoiser=temp_denoiser,
                                  nsteps_durgen=nsteps_durgen, nsteps_denoiser=nsteps_denoiser,
-                                 solver_denoiser=solver_denoiser)
+                                 solver_denoiser=solver_denoiser, exact_lengths=exact_lengths)
         per_sample = out["time"] / len(batch)
         for item, wav_t in zip(batch, out["wav"]):
             wav = wav_t[0].detach().cpu().numpy()
@@ -303,6 +306,9 @@ def build_arg_parser():
     p.add_argument("--solver-denoiser", type=str, default="euler", choices=["euler", "midpoint", "heun"],
                    help="Denoiser ODE solver; midpoint / heun are second order and --nsteps-denoiser (even) then "
                         "counts velocity evaluations.")
+    p.add_argument("--exact-lengths", type=str2bool, default=False,
+                   help="Fold and solve every utterance of a padded batch over its own frames only, so its latents do "
+                        "not depend on the batch it shares (default: False, the reference's padded batch).")
     p.add_argument("--temp-durgen", type=float, default=0.3, help="Duration generator temperature.")
     p.add_argument("--temp-denoiser", type=float, default=0.3, help="Denoiser temperature.")
     p.add_argument("--device", type=str, default="cuda:0", help="Device to run inference on.")
@@ -338,7 +344,8 @@ def main(args: Optional[argparse.Namespace] = None):
     common = dict(model=model, codec_encoder=codec_encoder, codec_decoder=codec_decoder, prompt_dir=args.prompt_dir,
                   output_dir=args.output_dir, nsteps_durgen=args.nsteps_durgen, nsteps_denoiser=args.nsteps_denoiser,
                   temp_durgen=args.temp_durgen, temp_denoiser=args.temp_denoiser, meter=meter,
-                  solver_denoiser=getattr(args, "solver_denoiser", "euler"))
+                  solver_denoiser=getattr(args, "solver_denoiser", "euler"),
+                  exact_lengths=bool(getattr(args, "exact_lengths", False)))
     if args.metadata_file:
         rtf = synthesize_with_metadata(metadata_file=args.metadata_file, skip_existing=args.skip_existing,
                                        batch_size=args.batch_size, **common)

@@ -119,6 +119,21 @@ FLAMED_API int flamed_den_solve_part(flamed_den_t h, float* xt, const float* mod
  * or a null pointer return 1001 with a flamed_last_error text.  There is no _part / _chunk form. */
 FLAMED_API int flamed_den_solve_rk2(flamed_den_t h, float* xt, const float* mods, int nsteps, double a, int B, int T,
                                     void* ws, size_t ws_bytes, int use_graph, hipStream_t stream);
+/* Exact lengths: the same solves for a padded ragged batch.  lens: B HOST ints, 2 <= lens[u] <= T.  Utterance u (rows
+ * u T .. u T + lens[u] - 1 of xt, modulation row u of every block) is solved over its own lens[u] frames, exactly as
+ * if it were alone at T = lens[u]: GroupNorm over lens[u] frames, the depthwise and conv_out zero padding at its own
+ * end.  Rows u T + lens[u] .. (u + 1) T - 1 of xt are neither read nor written (the caller zeroes or ignores them).
+ * Every length equal to T gives bitwise flamed_den_solve / _solve_rk2.  2..8 utterances that are eligible for the
+ * persistent solve below run as ONE persistent launch (its exact-lengths variants, same failure semantics: the valid
+ * rows are NaN-poisoned); everything else (fp32 / fp8 handles, B > 8, B x T > 4096, "persist" 0, use_graph bit 2, a
+ * refused cooperative grid) solves one utterance after another on plain launches.  ws as for (B, T), and at least
+ * flamed_den_workspace_size(h, 1, lens[u]) for every u.  A null pointer or a length outside 2..T returns 1001 with a
+ * flamed_last_error text before any pointer is touched (one frame alone is what the reference's GroupNorm over T
+ * refuses); flamed_den_solve_rk2's checks of nsteps and a apply unchanged. */
+FLAMED_API int flamed_den_solve_lens(flamed_den_t h, float* xt, const float* mods, const int* lens, int nfe, int B, int T,
+                                     void* ws, size_t ws_bytes, int use_graph, hipStream_t stream);
+FLAMED_API int flamed_den_solve_rk2_lens(flamed_den_t h, float* xt, const float* mods, const int* lens, int nsteps, double a,
+                                         int B, int T, void* ws, size_t ws_bytes, int use_graph, hipStream_t stream);
 /* The persistent solve (one launch of 256 workgroups for every step, flamed_tune "persist"; taken by
  * flamed_den_solve / _solve_part with use_graph != 0 on a bf16 handle for one utterance of 16..4096 frames,
  * or -- "persist_multi", default on -- for B = 2 / 4 / 8 equal-length utterances with B x T <= 4096 (and, knob
@@ -277,6 +292,11 @@ FLAMED_API int flamed_cond_load(flamed_cond_t h, const float* const* weights, in
 FLAMED_API size_t flamed_cond_workspace_size(flamed_cond_t h, int B, int T);
 FLAMED_API int flamed_cond_fold(flamed_cond_t h, const float* cond, const float* mask, int B, int T, float* out, void* ws,
                                 size_t ws_bytes, hipStream_t stream);
+/* Exact lengths (same arguments): both GroupNorm(8) take their statistics over the frames whose mask is 1 only, with
+ * that count, and the rows whose mask is 0 come out 0 -- so a prefix-masked utterance gets what flamed_cond_fold gives
+ * it alone at T = its length with a mask of ones (an utterance without a valid frame comes out all 0). */
+FLAMED_API int flamed_cond_fold_exact(flamed_cond_t h, const float* cond, const float* mask, int B, int T, float* out,
+                                      void* ws, size_t ws_bytes, hipStream_t stream);
 
 /* ==================== PVA duration / silence generators + length regulator ====================
  * Replaces ProbabilisticModule.forward (pva.py:221-238) inside the Euler loop of PVA.sample

@@ -5,7 +5,10 @@ the persistent launch ran, and whether the output equals (bitwise) the shape's f
 --solver midpoint|heun runs the two-stage second-order solve instead (the shape's last number stays the count of
 velocity evaluations).  --make-ref FILE computes, on the CPU in fp32 with the module's own torch ops, a converged
 solution (midpoint, --ref-steps steps) of utterance 0 of the one given shape and stores it; --ref FILE then prints
-each solve's rel-L2 error of utterance 0 against it (same shape and seeds, so the same inputs)."""
+each solve's rel-L2 error of utterance 0 against it (same shape and seeds, so the same inputs).
+--lens 800,611,437,250 (one shape, B = the number of lengths, T = the longest) runs the exact-lengths solve of the
+padded batch (DenoiserHIP.solve(..., lens=)); --alone then times instead the same utterances solved one after another,
+each alone at its own length (the sum is one "solve")."""
 import argparse
 import os
 import statistics
@@ -25,6 +28,8 @@ def main():
     ap.add_argument("--knobs", nargs="*", default=[""])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--solver", default="euler", choices=["euler", "midpoint", "heun"])
+    ap.add_argument("--lens", default=None)
+    ap.add_argument("--alone", action="store_true")
     ap.add_argument("--ref", default=None)
     ap.add_argument("--make-ref", default=None)
     ap.add_argument("--ref-steps", type=int, default=128)
@@ -46,13 +51,23 @@ def main():
         B, T, nfe = (int(v) for v in shape.split("x"))
         x0, spk = (v.to(dev) for v in inputs(B, T))
         stage = SOLVERS[a.solver]
+        lens = [int(v) for v in a.lens.split(",")] if a.lens else None
+        if lens is not None and (len(lens) != B or max(lens) != T):
+            raise SystemExit(f"--lens {a.lens}: the shape must be {len(lens)}x{max(lens)}x<nfe>")
+        kw = {} if lens is None or a.alone else {"lens": lens}
         if stage is None:
             ts = torch.linspace(0, 1, nfe + 1, device=dev)
-            solve = lambda: hip.solve(x0, ts, spk, nfe)  # noqa: E731
+            one = lambda x, c: hip.solve(x, ts, c, nfe, **kw)  # noqa: E731
         else:
             tb = torch.linspace(0, 1, nfe // 2 + 1, device=dev)[:-1]
             ts = torch.stack((tb, tb + stage * (1 / (nfe // 2))), dim=1).reshape(-1)
-            solve = lambda: hip.solve_rk2(x0, ts, spk, nfe // 2, stage)  # noqa: E731
+            one = lambda x, c: hip.solve_rk2(x, ts, c, nfe // 2, stage, **kw)  # noqa: E731
+        if lens is not None and a.alone:  # every utterance alone at its own length, one after another
+            parts = [(x0[u:u + 1, :n].contiguous(), spk[u:u + 1]) for u, n in enumerate(lens)]
+            solve = lambda: torch.cat([torch.nn.functional.pad(one(x, c), (0, 0, 0, T - x.shape[1])) for x, c in parts])  # noqa: E731
+        else:
+            solve = lambda: one(x0, spk)  # noqa: E731
+        per = len(lens) if lens is not None and a.alone else 1  # persistent launches of one "solve"
         conv = torch.from_numpy(np.load(a.ref)).double() if a.ref else None
         first = None
         for kn in a.knobs:
@@ -73,13 +88,16 @@ def main():
             if first is None:
                 first = ref.clone()
             err = ""
-            if runs == a.reps:  # device time of the persistent launches themselves (HIP events around each kernel)
+            if runs == a.reps * per and per > 1:
+                err = f", persistent kernels {sum(hip.persist_times(a.reps * per)) / a.reps:.3f} ms per {per} solves"
+            elif runs == a.reps:  # device time of the persistent launches themselves (HIP events around each kernel)
                 dev_ms = statistics.median(hip.persist_times(a.reps))
                 err = f", persistent kernel {dev_ms:.3f} ms = {1e3 * dev_ms / nfe:.1f} us per evaluation"
             if conv is not None:
                 d = ref[0].double().cpu() - conv
                 err += f", rel-L2 of utterance 0 vs the converged solution {float(d.norm() / conv.norm()):.3e}"
-            print(f"B={B} T={T} nfe={nfe} {a.solver} [{kn or 'defaults'}]: {statistics.median(times):.2f} ms/solve "
+            form = "" if lens is None else f" lens {a.lens} ({'each alone' if a.alone else 'exact lengths, one call'})"
+            print(f"B={B} T={T} nfe={nfe} {a.solver}{form} [{kn or 'defaults'}]: {statistics.median(times):.2f} ms/solve "
                   f"(min {min(times):.2f}), persistent launches {runs}/{a.reps}, finite {bool(torch.isfinite(ref).all())}, "
                   f"equal to the first knob set {bool(torch.equal(ref, first))}"
                   f"{err}{chain_info(L, hip)}", flush=True)
