@@ -63,12 +63,23 @@ __global__ void pack_convt_kernel(const float* __restrict__ src, DT* __restrict_
 // ------------------------------ fused Activation1d ------------------------------
 constexpr int kActA = 64;  // output samples per workgroup
 
-// kActCG channels per workgroup (64, or 32 for the encoder's first stage)
+// Exact lengths (flamed_fac_decode_lens): utterance b of the padded batch holds lens[b] frames, so at a stage that has
+// upsampled by `mul` its rows are [0, lens[b] * mul) of its n.  Every kernel below decides its edges (replicate clamp,
+// zero pad, last row written) from that end `ne`; the batch stride stays n, and the rows from ne on are neither read
+// nor written (the wav samples there are written as 0).  The dense kernels pass ne = n.
+struct FacLens {
+  const int* __restrict__ lens;  // B device ints, 1 <= lens[b] <= T (handle-owned, filled stream-ordered per call)
+  int mul;
+  __device__ int end(int b) const { return lens[b] * mul; }
+};
+
+// kActCG channels per workgroup (64, or 32 for the encoder's first stage); n = batch stride in rows, ne = this
+// utterance's own end (ne <= n; a0 < ne)
 template <typename OT, int kActCG>
-__global__ __launch_bounds__(256) void act1d_kernel(const float* __restrict__ x, int C, int n,
-                                                    const float* __restrict__ alpha, const float* __restrict__ beta,
-                                                    const float* __restrict__ fu, const float* __restrict__ fd,
-                                                    OT* __restrict__ out) {
+__device__ __forceinline__ void act1d_body(const float* __restrict__ x, int C, int n, int ne,
+                                           const float* __restrict__ alpha, const float* __restrict__ beta,
+                                           const float* __restrict__ fu, const float* __restrict__ fd,
+                                           OT* __restrict__ out) {
   constexpr int XR = kActA + 13;      // x rows a0-6 .. a0+A+6
   constexpr int SR = 2 * kActA + 12;  // snake samples j = 2a0-5 .. 2a0+2A+6
   constexpr int RGS = 256 / kActCG;   // row groups
@@ -83,14 +94,14 @@ __global__ __launch_bounds__(256) void act1d_kernel(const float* __restrict__ x,
   for (int idx = tid; idx < XR * kActCG; idx += 256) {
     int r = idx / kActCG, cc = idx - r * kActCG;
     int a = a0 - 6 + r;
-    a = a < 0 ? 0 : (a >= n ? n - 1 : a);
+    a = a < 0 ? 0 : (a >= ne ? ne - 1 : a);
     xs[idx] = xb[(size_t)a * C + c0 + cc];
   }
   __syncthreads();
   const int cc = tid % kActCG, rg = tid / kActCG;
   const float ea = expf(alpha[c0 + cc]);
   const float ib = 1.0f / (expf(beta[c0 + cc]) + 1e-9f);
-  const int n2 = 2 * n;
+  const int n2 = 2 * ne;
   for (int jj = rg; jj < SR; jj += RGS) {
     int j = 2 * a0 - 5 + jj;
     j = j < 0 ? 0 : (j >= n2 ? n2 - 1 : j);
@@ -112,7 +123,7 @@ __global__ __launch_bounds__(256) void act1d_kernel(const float* __restrict__ x,
   OT* ob = out + (size_t)b * n * C;
   for (int q = rg; q < kActA; q += RGS) {
     int a = a0 + q;
-    if (a >= n) break;
+    if (a >= ne) break;
     float acc = 0.f;
 #pragma unroll
     for (int k = 0; k < 12; ++k) acc += filt[12 + k] * ss[(2 * q + k) * kActCG + cc];
@@ -120,21 +131,41 @@ __global__ __launch_bounds__(256) void act1d_kernel(const float* __restrict__ x,
   }
 }
 
+template <typename OT, int kActCG>
+__global__ __launch_bounds__(256) void act1d_kernel(const float* __restrict__ x, int C, int n,
+                                                    const float* __restrict__ alpha, const float* __restrict__ beta,
+                                                    const float* __restrict__ fu, const float* __restrict__ fd,
+                                                    OT* __restrict__ out) {
+  act1d_body<OT, kActCG>(x, C, n, n, alpha, beta, fu, fd, out);
+}
+
+// exact lengths: a workgroup whose tile starts at or past its utterance's end has nothing to do (blockIdx-uniform)
+template <typename OT, int kActCG>
+__global__ __launch_bounds__(256) void act1d_lens_kernel(const float* __restrict__ x, int C, int n, FacLens fl,
+                                                         const float* __restrict__ alpha, const float* __restrict__ beta,
+                                                         const float* __restrict__ fu, const float* __restrict__ fd,
+                                                         OT* __restrict__ out) {
+  const int ne = fl.end(blockIdx.z);
+  if ((int)blockIdx.y * kActA >= ne) return;
+  act1d_body<OT, kActCG>(x, C, n, ne, alpha, beta, fu, fd, out);
+}
+
 // ------------------------------ prep: LayerNorm over C + timbre affine + transpose ------------------------------
 // lat (B, C, T) channels-first -> h0 (B*T, C): LN(eps 1e-5, no affine) then x*gamma + beta (facodec.py:631-636)
-__global__ __launch_bounds__(256) void fac_prep_kernel(const float* __restrict__ lat, const float* __restrict__ style,
-                                                       int C, int T, float* __restrict__ h0) {
+// Te = this utterance's own frame count (T in the dense call): frames from Te on are neither loaded nor normalised
+__device__ __forceinline__ void fac_prep_body(const float* __restrict__ lat, const float* __restrict__ style, int C, int T,
+                                              int Te, float* __restrict__ h0) {
   extern __shared__ float tile[];  // C x 33
   const int b = blockIdx.y, t0 = blockIdx.x * 32, tid = threadIdx.x;
   for (int idx = tid; idx < C * 32; idx += 256) {
     int c = idx >> 5, t = idx & 31;
-    tile[c * 33 + t] = (t0 + t < T) ? lat[((size_t)b * C + c) * T + t0 + t] : 0.f;
+    tile[c * 33 + t] = (t0 + t < Te) ? lat[((size_t)b * C + c) * T + t0 + t] : 0.f;
   }
   __syncthreads();
   const int wave = tid >> 6, lane = tid & 63;
   const int per = C / 64;
   for (int t = wave; t < 32; t += 4) {
-    if (t0 + t >= T) break;
+    if (t0 + t >= Te) break;
     float v[8];
     float s = 0.f;
     for (int j = 0; j < per; ++j) {
@@ -156,10 +187,23 @@ __global__ __launch_bounds__(256) void fac_prep_kernel(const float* __restrict__
   }
 }
 
+__global__ __launch_bounds__(256) void fac_prep_kernel(const float* __restrict__ lat, const float* __restrict__ style,
+                                                       int C, int T, float* __restrict__ h0) {
+  fac_prep_body(lat, style, C, T, T, h0);
+}
+
+__global__ __launch_bounds__(256) void fac_prep_lens_kernel(const float* __restrict__ lat, const float* __restrict__ style,
+                                                            int C, int T, FacLens fl, float* __restrict__ h0) {
+  const int Te = fl.end(blockIdx.y);
+  if ((int)blockIdx.x * 32 >= Te) return;
+  fac_prep_body(lat, style, C, T, Te, h0);
+}
+
 // ------------------------------ final Conv1d(64 -> 1, k7, pad 3) + tanh ------------------------------
+// ne = this utterance's own end (n in the dense call): taps from ne on are zero, samples ne .. n - 1 are written as 0
 template <typename IT>
-__global__ __launch_bounds__(128) void fac_out_kernel(const IT* __restrict__ act, int C, int n, const float* __restrict__ w,
-                                                      const float* __restrict__ bias, float* __restrict__ wav) {
+__device__ __forceinline__ void fac_out_body(const IT* __restrict__ act, int C, int n, int ne, const float* __restrict__ w,
+                                             const float* __restrict__ bias, float* __restrict__ wav) {
   constexpr int TS = 128, HALO = 3;
   extern __shared__ float sm[];
   float* rows = sm;                      // (TS + 6) x (C + 1)
@@ -170,16 +214,40 @@ __global__ __launch_bounds__(128) void fac_out_kernel(const IT* __restrict__ act
   for (int idx = tid; idx < (TS + 2 * HALO) * C; idx += TS) {
     int r = idx / C, c = idx - r * C;
     int t = t0 - HALO + r;
-    rows[r * (C + 1) + c] = (t >= 0 && t < n) ? (float)ab[(size_t)t * C + c] : 0.f;
+    rows[r * (C + 1) + c] = (t >= 0 && t < ne) ? (float)ab[(size_t)t * C + c] : 0.f;
   }
   __syncthreads();
   const int t = t0 + tid;
   if (t >= n) return;
+  if (t >= ne) {
+    wav[(size_t)b * n + t] = 0.f;
+    return;
+  }
   float acc = bias[0];
   for (int c = 0; c < C; ++c)
 #pragma unroll
     for (int k = 0; k < 7; ++k) acc += ws[c * 7 + k] * rows[(tid + k) * (C + 1) + c];
   wav[(size_t)b * n + t] = tanhf(acc);
+}
+
+template <typename IT>
+__global__ __launch_bounds__(128) void fac_out_kernel(const IT* __restrict__ act, int C, int n, const float* __restrict__ w,
+                                                      const float* __restrict__ bias, float* __restrict__ wav) {
+  fac_out_body<IT>(act, C, n, n, w, bias, wav);
+}
+
+// exact lengths: the wav buffer is reused between calls, so a tile past the utterance's end writes its zeros
+template <typename IT>
+__global__ __launch_bounds__(128) void fac_out_lens_kernel(const IT* __restrict__ act, int C, int n, FacLens fl,
+                                                           const float* __restrict__ w, const float* __restrict__ bias,
+                                                           float* __restrict__ wav) {
+  const int ne = fl.end(blockIdx.y);
+  const int t = blockIdx.x * 128 + threadIdx.x;
+  if ((int)blockIdx.x * 128 >= ne) {  // blockIdx-uniform
+    if (t < n) wav[(size_t)blockIdx.y * n + t] = 0.f;
+    return;
+  }
+  fac_out_body<IT>(act, C, n, ne, w, bias, wav);
 }
 
 // ------------------------------ GEMM loaders / epilogues ------------------------------
@@ -215,6 +283,97 @@ struct EpiConvTStore {
     int b = m / (n + 1), q = m - b * (n + 1);
     int o = q * s + r - p;
     if (o >= 0 && o < s * n) out[((size_t)b * s * n + o) * Cout + col] = v;
+  }
+  __device__ void store_stats(int, int, float, float) const {}
+};
+
+// ---- exact-lengths forms: a tap is zero when its source row is outside [0, ne) of its utterance; a row at or past
+// ne loads nothing (its result is never read by a valid row: a GEMM row depends on its own A row only).
+
+// conv_in: Conv1d(k = KT, pad KT/2) over the fp32 styled-LayerNorm rows h0 (B*T, Cin), packed to DT
+template <typename DT>
+struct LoadConvInLens {
+  const float* __restrict__ x;
+  int Cin, L, KT;
+  FacLens fl;
+  static constexpr int EPC = DTraits<DT>::EPC;
+  struct Raw { float v[EPC]; };
+  static constexpr int stat_rows(int) { return 0; }
+  __device__ void prologue(int, int, int, float*) const {}
+  __device__ Raw issue(int m, int k) const {
+    Raw r;
+    const int b = m / L, l = m - b * L, ne = fl.end(b);
+    const int tap = k / Cin, c = k - tap * Cin;
+    const int off = tap - KT / 2;
+    const int i = l + off;
+    if (l < ne && i >= 0 && i < ne) {
+      const float* px = x + (size_t)(m + off) * Cin + c;
+#pragma unroll
+      for (int j = 0; j < EPC; j += 4) {
+        float4 a = ld4(px + j);
+        r.v[j] = a.x; r.v[j + 1] = a.y; r.v[j + 2] = a.z; r.v[j + 3] = a.w;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < EPC; ++j) r.v[j] = 0.f;
+    }
+    return r;
+  }
+  template <typename D> __device__ u32x4 finish(const Raw& r, int, int, const float*, int) const { return pack_chunk<D>(r.v); }
+};
+
+// dilated k7 conv of a residual unit over the DT activation (B*L, Cin)
+template <typename DT>
+struct LoadConvPlainLens {
+  const DT* __restrict__ x;
+  int Cin, L, KT, dil;
+  FacLens fl;
+  struct Raw { u32x4 v; };
+  static constexpr int stat_rows(int) { return 0; }
+  __device__ void prologue(int, int, int, float*) const {}
+  __device__ Raw issue(int m, int k) const {
+    const int b = m / L, l = m - b * L, ne = fl.end(b);
+    const int tap = k / Cin, c = k - tap * Cin;
+    const int off = (tap - KT / 2) * dil;
+    const int i = l + off;
+    if (l >= ne || i < 0 || i >= ne) return Raw{u32x4{0u, 0u, 0u, 0u}};
+    return Raw{*reinterpret_cast<const u32x4*>(x + (size_t)(m + off) * Cin + c)};
+  }
+  template <typename D> __device__ u32x4 finish(const Raw& r, int, int, const float*, int) const { return r.v; }
+};
+
+// LoadConvT with the utterance's own end: q in [0, ne] has sources, tap 1 of q = ne reads x[ne - 1]
+template <typename DT>
+struct LoadConvTLens {
+  const DT* __restrict__ x;
+  int Cin, n;
+  FacLens fl;
+  struct Raw { u32x4 v; };
+  static constexpr int stat_rows(int) { return 0; }
+  __device__ void prologue(int, int, int, float*) const {}
+  __device__ Raw issue(int m, int k) const {
+    const int b = m / (n + 1), q = m - b * (n + 1), ne = fl.end(b);
+    const int tap = k / Cin, c = k - tap * Cin;
+    const int i = q - tap;
+    if (i < 0 || i >= ne) return Raw{u32x4{0u, 0u, 0u, 0u}};
+    return Raw{*reinterpret_cast<const u32x4*>(x + ((size_t)b * n + i) * Cin + c)};
+  }
+  template <typename D> __device__ u32x4 finish(const Raw& r, int, int, const float*, int) const { return r.v; }
+};
+
+struct EpiConvTStoreLens {  // EpiConvTStore that stores o < s * ne only
+  const float* __restrict__ bias;
+  float* __restrict__ out;
+  int Cout, n, s, r, p;
+  FacLens fl;
+  static constexpr bool kRowStats = false;
+  static constexpr int stat_rows(int) { return 0; }
+  __device__ void prologue(int, int, int, float*) const {}
+  __device__ float value(int, int col, float acc, const float*, int) const { return acc + bias[col]; }
+  __device__ void store(int m, int col, float v) const {
+    int b = m / (n + 1), q = m - b * (n + 1);
+    int o = q * s + r - p;
+    if (o >= 0 && o < s * fl.end(b)) out[((size_t)b * s * n + o) * Cout + col] = v;
   }
   __device__ void store_stats(int, int, float, float) const {}
 };
@@ -256,12 +415,22 @@ struct Fac {
   hipGraphExec_t gexec = nullptr;
   hipStream_t cap = nullptr;
   std::vector<const void*> gkey;
+  // exact lengths: a graph of its own (the dense and the ragged call of one (B, T) never replay each other's) whose
+  // kernels read this call's lengths from dlens, filled stream-ordered ahead of the replay
+  hipGraphExec_t gexec_l = nullptr;
+  std::vector<const void*> gkey_l;
+  int* dlens = nullptr;
+  int dlens_cap = 0;
   void release() {
     retire_graph(gexec);
+    retire_graph(gexec_l);
     if (cap) (void)hipStreamDestroy(cap);
     if (dev) (void)hipFree(dev);
-    gexec = nullptr; cap = nullptr; dev = nullptr;
+    if (dlens) (void)hipFree(dlens);
+    gexec = nullptr; gexec_l = nullptr; cap = nullptr; dev = nullptr; dlens = nullptr;
+    dlens_cap = 0;
     gkey.clear();
+    gkey_l.clear();
   }
 };
 
@@ -302,41 +471,111 @@ static int launch_act(const FacAct& a, const float* x, int C, int n, int B, DT* 
 }
 
 template <typename DT>
+static int launch_act_lens(const FacAct& a, const float* x, int C, int n, int B, FacLens fl, DT* out, hipStream_t st) {
+  FL_REQUIRE(C % 64 == 0, "act1d: C=%d must be a multiple of 64", C);
+  const int na = (n + kActA - 1) / kActA;
+  hipLaunchKernelGGL((act1d_lens_kernel<DT, 64>), dim3(C / 64, na, B), dim3(256), 0, st, x, C, n, fl, a.alpha, a.beta, a.fu, a.fd, out);
+  FL_LAUNCH_CHECK();
+  return kOk;
+}
+
+// This call's lengths travel as a kernel argument (copied at launch, so the caller's array may go at once) and are
+// written to the handle's device array in stream order, ahead of the kernels (or the graph replay) that read them.
+constexpr int kLensChunk = 64;
+struct LensArg { int v[kLensChunk]; };
+__global__ __launch_bounds__(kLensChunk) void fac_set_lens_kernel(LensArg a, int cnt, int* __restrict__ dst) {
+  const int i = threadIdx.x;
+  if (i < cnt) dst[i] = a.v[i];
+}
+
+static int fac_set_lens(Fac* f, const int* lens, int B, hipStream_t st) {
+  if (B > f->dlens_cap) {  // grows only; the pointer is part of the ragged graph's key
+    retire_graph(f->gexec_l);
+    f->gkey_l.clear();
+    if (f->dlens) FL_HIP(hipFree(f->dlens));  // (waits for the work that may still read it)
+    f->dlens = nullptr;
+    f->dlens_cap = 0;
+    const int cap = (B + kLensChunk - 1) / kLensChunk * kLensChunk;
+    FL_HIP(hipMalloc(&f->dlens, sizeof(int) * cap));
+    f->dlens_cap = cap;
+  }
+  for (int b0 = 0; b0 < B; b0 += kLensChunk) {
+    LensArg a;
+    const int cnt = B - b0 < kLensChunk ? B - b0 : kLensChunk;
+    for (int i = 0; i < kLensChunk; ++i) a.v[i] = i < cnt ? lens[b0 + i] : 0;
+    hipLaunchKernelGGL(fac_set_lens_kernel, dim3(1), dim3(kLensChunk), 0, st, a, cnt, f->dlens + b0);
+    FL_LAUNCH_CHECK();
+  }
+  return kOk;
+}
+
+// RAG: the exact-lengths decode -- the same launches with the kernels and loaders that take each utterance's own end
+// from `lens` (B device ints); the dense instantiation (RAG = false) is the decode as it always was.
+template <typename DT, bool RAG = false>
 static int fac_decode_impl(Fac* f, const float* lat, const float* spk, int B, int T, float* wav, const FacWs& w,
-                           hipStream_t st) {
+                           hipStream_t st, const int* lens = nullptr) {
   int rc;
 #define TRY(x) do { if ((rc = (x)) != kOk) return rc; } while (0)
   const int C0 = f->C0;
   DT* A = reinterpret_cast<DT*>(w.A);
   TRY((launch_gemm<float>(LoadF32<float>{spk, C0}, f->tlw, C0, EpiBiasAct<float, 0>{f->tlb, w.style, 2 * C0}, B, 2 * C0, C0, st)));
-  hipLaunchKernelGGL(fac_prep_kernel, dim3((T + 31) / 32, B), dim3(256), (size_t)C0 * 33 * 4, st, lat, w.style, C0, T, w.h0);
-  FL_LAUNCH_CHECK();
-  TRY((gemm_auto<DT>(LoadConvRows<DT, false>{w.h0, C0, T, 7, 1, nullptr, 0, 0, 0.f, nullptr, nullptr}, (const DT*)f->win, 7 * C0,
-                     EpiBiasAct<float, 0>{f->bin, w.X, f->CI}, B * T, f->CI, 7 * C0, st)));
-  int n = T;
+  if constexpr (RAG) {
+    const FacLens fl0{lens, 1};
+    hipLaunchKernelGGL(fac_prep_lens_kernel, dim3((T + 31) / 32, B), dim3(256), (size_t)C0 * 33 * 4, st, lat, w.style, C0, T, fl0,
+                       w.h0);
+    FL_LAUNCH_CHECK();
+    TRY((gemm_auto<DT>(LoadConvInLens<DT>{w.h0, C0, T, 7, FacLens{lens, 1}}, (const DT*)f->win, 7 * C0,
+                       EpiBiasAct<float, 0>{f->bin, w.X, f->CI}, B * T, f->CI, 7 * C0, st)));
+  } else {
+    hipLaunchKernelGGL(fac_prep_kernel, dim3((T + 31) / 32, B), dim3(256), (size_t)C0 * 33 * 4, st, lat, w.style, C0, T, w.h0);
+    FL_LAUNCH_CHECK();
+    TRY((gemm_auto<DT>(LoadConvRows<DT, false>{w.h0, C0, T, 7, 1, nullptr, 0, 0, 0.f, nullptr, nullptr}, (const DT*)f->win, 7 * C0,
+                       EpiBiasAct<float, 0>{f->bin, w.X, f->CI}, B * T, f->CI, 7 * C0, st)));
+  }
+  // Activation1d at a stage whose rows are n = T * mul per utterance
+  auto act = [&](const FacAct& a, const float* x, int C, int n, int mul) -> int {
+    if constexpr (RAG) return launch_act_lens<DT>(a, x, C, n, B, FacLens{lens, mul}, A, st);
+    else return launch_act<DT>(a, x, C, n, B, A, st);
+  };
+  int n = T, mul = 1;
   for (int i = 0; i < f->NUP; ++i) {
     const FacBlk& bk = f->blk[i];
     const int s = bk.s, Cin = bk.cin, Cout = bk.cout, p = s / 2 + s % 2;
-    TRY(launch_act<DT>(bk.a, w.X, Cin, n, B, A, st));
+    TRY(act(bk.a, w.X, Cin, n, mul));
     for (int r = 0; r < s; ++r) {
       const DT* Wr = (const DT*)bk.wt + (size_t)r * Cout * 2 * Cin;
-      TRY((gemm_auto<DT>(LoadConvT<DT>{A, Cin, n}, Wr, 2 * Cin, EpiConvTStore{bk.bt, w.X, Cout, n, s, r, p}, B * (n + 1), Cout,
-                         2 * Cin, st)));
+      if constexpr (RAG)
+        TRY((gemm_auto<DT>(LoadConvTLens<DT>{A, Cin, n, FacLens{lens, mul}}, Wr, 2 * Cin,
+                           EpiConvTStoreLens{bk.bt, w.X, Cout, n, s, r, p, FacLens{lens, mul}}, B * (n + 1), Cout, 2 * Cin, st)));
+      else
+        TRY((gemm_auto<DT>(LoadConvT<DT>{A, Cin, n}, Wr, 2 * Cin, EpiConvTStore{bk.bt, w.X, Cout, n, s, r, p}, B * (n + 1), Cout,
+                           2 * Cin, st)));
     }
     n *= s;
+    mul *= s;
     for (int j = 0; j < 3; ++j) {
       const FacRU& ru = bk.ru[j];
-      TRY(launch_act<DT>(ru.a1, w.X, Cout, n, B, A, st));
-      TRY((gemm_auto<DT>(LoadConvPlain<DT>{A, Cout, n, 7, ru.dil}, (const DT*)ru.w7, 7 * Cout,
-                         EpiBiasAct<float, 0>{ru.b7, w.Z, Cout}, B * n, Cout, 7 * Cout, st)));
-      TRY(launch_act<DT>(ru.a2, w.Z, Cout, n, B, A, st));
+      TRY(act(ru.a1, w.X, Cout, n, mul));
+      if constexpr (RAG)
+        TRY((gemm_auto<DT>(LoadConvPlainLens<DT>{A, Cout, n, 7, ru.dil, FacLens{lens, mul}}, (const DT*)ru.w7, 7 * Cout,
+                           EpiBiasAct<float, 0>{ru.b7, w.Z, Cout}, B * n, Cout, 7 * Cout, st)));
+      else
+        TRY((gemm_auto<DT>(LoadConvPlain<DT>{A, Cout, n, 7, ru.dil}, (const DT*)ru.w7, 7 * Cout,
+                           EpiBiasAct<float, 0>{ru.b7, w.Z, Cout}, B * n, Cout, 7 * Cout, st)));
+      TRY(act(ru.a2, w.Z, Cout, n, mul));
+      // the 1x1 conv has no edge: a row reads its own row only (rows past an utterance's end hold anything)
       TRY((gemm_auto<DT>(LoadPlain<DT>{A, Cout}, (const DT*)ru.w1, Cout, EpiResAdd{ru.b1, w.X, Cout}, B * n, Cout, Cout, st)));
     }
   }
   const int cf = f->cfin;
-  TRY(launch_act<DT>(f->afin, w.X, cf, n, B, A, st));
+  TRY(act(f->afin, w.X, cf, n, mul));
   size_t smem = ((128 + 6) * (cf + 1) + cf * 7) * 4;
-  hipLaunchKernelGGL(fac_out_kernel<DT>, dim3((n + 127) / 128, B), dim3(128), smem, st, A, cf, n, f->wout, f->bout, wav);
+  if constexpr (RAG) {
+    const FacLens flo{lens, mul};
+    hipLaunchKernelGGL(fac_out_lens_kernel<DT>, dim3((n + 127) / 128, B), dim3(128), smem, st, A, cf, n, flo, f->wout, f->bout, wav);
+  } else {
+    hipLaunchKernelGGL(fac_out_kernel<DT>, dim3((n + 127) / 128, B), dim3(128), smem, st, A, cf, n, f->wout, f->bout, wav);
+  }
   FL_LAUNCH_CHECK();
 #undef TRY
   return kOk;
@@ -485,6 +724,7 @@ FLAMED_API int flamed_fac_load(flamed_fac_t h, const float* const* w, int nw, hi
   }
   FL_HIP(hipStreamSynchronize(st));  // the fold scratch is reused per conv on the same stream; drain before returning
   retire_graph(f->gexec);
+  retire_graph(f->gexec_l);
   return kOk;
 }
 
@@ -531,6 +771,61 @@ FLAMED_API int flamed_fac_decode(flamed_fac_t h, const float* latents, const flo
   }
   FL_HIP(hipGraphLaunch(f->gexec, st));
   note_graph_use(f->gexec, st);
+  return kOk;
+}
+
+FLAMED_API int flamed_fac_decode_lens(flamed_fac_t h, const float* latents, const float* spk, int B, int T, const int* lens,
+                                      float* wav, void* ws, size_t ws_bytes, int use_graph, hipStream_t st) {
+  // every check of the arguments comes before any pointer is touched
+  FL_REQUIRE(h && latents && spk && lens && wav && ws, "flamed_fac_decode_lens: null handle, latents, speaker, lengths, wav or workspace");
+  FL_REQUIRE(B > 0 && T > 0, "flamed_fac_decode_lens: bad dims B=%d T=%d", B, T);
+  bool dense = true;
+  for (int u = 0; u < B; ++u) {
+    FL_REQUIRE(lens[u] >= 1 && lens[u] <= T, "flamed_fac_decode_lens: utterance %d has length %d (1..T = %d)", u, lens[u], T);
+    dense = dense && lens[u] == T;
+  }
+  if (dense) return flamed_fac_decode(h, latents, spk, B, T, wav, ws, ws_bytes, use_graph, st);  // the dense call itself
+  Fac* f = reinterpret_cast<Fac*>(h);
+  FL_REQUIRE(f->dev, "flamed_fac_decode_lens: handle not loaded");
+  std::lock_guard<std::mutex> lk(f->mu);
+  FL_ON_DEVICE(f->device);
+  FL_REQUIRE_ON(latents, f->device, "flamed_fac_decode_lens");
+  const Tune tsnap = tune_snapshot(nullptr);
+  TuneScope ts_(&tsnap);
+  if (ws_bytes < fac_ws_layout(f, B, T, nullptr, nullptr)) {
+    set_error("flamed_fac_decode_lens: workspace too small");
+    return kNoWorkspace;
+  }
+  FacWs w;
+  fac_ws_layout(f, B, T, ws, &w);
+  {
+    const int rc = fac_set_lens(f, lens, B, st);  // stream-ordered ahead of the kernels / the replay below
+    if (rc) return rc;
+  }
+  const int* dl = f->dlens;
+  auto run = [&](hipStream_t s) -> int {
+    return f->dt == FLAMED_BF16 ? fac_decode_impl<bf16, true>(f, latents, spk, B, T, wav, w, s, dl)
+                                : fac_decode_impl<float, true>(f, latents, spk, B, T, wav, w, s, dl);
+  };
+  if (!use_graph) return run(st);
+  // the graph holds no length: one capture per (pointers, B, T) serves every ragged call of that shape
+  std::vector<const void*> key = {latents, spk, wav, ws, (const void*)(intptr_t)B, (const void*)(intptr_t)T, f->dev, dl};
+  if (!f->gexec_l || f->gkey_l != key) {
+    retire_graph(f->gexec_l);
+    if (!f->cap) FL_HIP(hipStreamCreateWithFlags(&f->cap, hipStreamNonBlocking));
+    FL_HIP(hipStreamBeginCapture(f->cap, hipStreamCaptureModeRelaxed));
+    int r = run(f->cap);
+    hipGraph_t g = nullptr;
+    hipError_t e = hipStreamEndCapture(f->cap, &g);
+    if (r) { if (g) (void)hipGraphDestroy(g); return r; }
+    FL_HIP(e);
+    hipError_t ie = hipGraphInstantiate(&f->gexec_l, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    FL_HIP(ie);
+    f->gkey_l = key;
+  }
+  FL_HIP(hipGraphLaunch(f->gexec_l, st));
+  note_graph_use(f->gexec_l, st);
   return kOk;
 }
 

@@ -24,6 +24,7 @@ from typing import Dict, List
 import numpy as np
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 from torch.nn.utils import weight_norm
 
 from flamed import _native as nat
@@ -339,15 +340,59 @@ class FACodecDecoder(nn.Module):
             out = out + self.quantizer[2].vq2emb(vq[p + c:])
         return out
 
-    def inference(self, x, speaker_embedding):
-        """latents (B, in_channels, T), speaker (B, in_channels) -> wav (B, 1, hop*T)."""
+    def inference(self, x, speaker_embedding, lens=None):
+        """latents (B, in_channels, T), speaker (B, in_channels) -> wav (B, 1, hop*T).
+
+        lens (exact lengths; B integers in 1..T, a sequence or a 1-D integer tensor): utterance u of the padded batch
+        is decoded over its own lens[u] frames, so wav[u, :, :hop*lens[u]] is inference(x[u:u+1, :, :lens[u]],
+        speaker_embedding[u:u+1]) and wav[u, :, hop*lens[u]:] is exactly 0; nothing stored in x[u, :, lens[u]:] is
+        read.  Every length equal to T is the call without lens."""
+        if lens is not None:
+            lens = check_lens(lens, x.shape[0], x.shape[2])
+            if all(n == x.shape[2] for n in lens):
+                lens = None
         if self._use_hip(x):
             if self._hip is None or self._hip.dtype_name != self.hip_dtype:
                 self._hip = FacDecoderHIP(self, self.hip_dtype)
+            if lens is not None:
+                return ops.fac_decode_lens(self._hip.oid, x, speaker_embedding, lens)
             return ops.fac_decode(self._hip.oid, x, speaker_embedding)
+        if lens is not None:  # the definition: one utterance after another, alone
+            T, hop = x.shape[2], self.hop_length
+            return torch.cat([F.pad(self._inference_torch(x[u:u + 1, :, :n], speaker_embedding[u:u + 1]), (0, hop * (T - n)))
+                              for u, n in enumerate(lens)], dim=0)
+        return self._inference_torch(x, speaker_embedding)
+
+    def _inference_torch(self, x, speaker_embedding):
         gamma, beta = self.timbre_linear(speaker_embedding).unsqueeze(2).chunk(2, 1)
         h = self.timbre_norm(x.transpose(1, 2)).transpose(1, 2)
         return self.model(h * gamma + beta)
+
+
+def check_lens(lens, B: int, T: int) -> List[int]:
+    """The lengths of an exact-lengths decode as a list of B ints in 1..T; ValueError otherwise (a wrong count, a
+    non-integer, a length outside 1..T), before anything is launched."""
+    if isinstance(lens, torch.Tensor):
+        if lens.dim() != 1 or lens.dtype.is_floating_point or lens.dtype.is_complex or lens.dtype == torch.bool:
+            raise ValueError(f"lens must be a 1-D integer tensor, got shape {tuple(lens.shape)} dtype {lens.dtype}")
+        lens = lens.tolist()
+    else:
+        try:
+            lens = list(lens)
+        except TypeError:
+            raise ValueError(f"lens must be a sequence of {B} integers or a 1-D integer tensor, got {type(lens).__name__}") from None
+    if len(lens) != B:
+        raise ValueError(f"lens holds {len(lens)} lengths for a batch of {B}")
+    out = []
+    for u, n in enumerate(lens):
+        if isinstance(n, torch.Tensor) and n.numel() == 1 and not (n.dtype.is_floating_point or n.dtype == torch.bool):
+            n = n.item()
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+            raise ValueError(f"lens[{u}] = {n!r} is not an integer")
+        if not 1 <= int(n) <= T:
+            raise ValueError(f"lens[{u}] = {int(n)} is outside 1..T = {T}")
+        out.append(int(n))
+    return out
 
 
 def fac_weight_list(dec: FACodecDecoder) -> List[torch.Tensor]:
@@ -413,7 +458,10 @@ class FacDecoderHIP:
         self._sig = sig
         self._bufs = {}
 
-    def decode(self, x, spk):
+    def decode(self, x, spk, lens=None):
+        """lens: None, or B ints in 1..T (flamed_fac_decode_lens: each utterance over its own frames, 0 behind it)."""
+        if lens is not None:
+            lens = check_lens(lens, x.shape[0], x.shape[2])
         dev = x.device
         self._ensure(dev)
         B, C, T = x.shape
@@ -428,9 +476,15 @@ class FacDecoderHIP:
         bufs["s"].copy_(spk)
         L = nat.lib()
         ws = self.ws.get(L.flamed_fac_workspace_size(self.handle, B, T), dev)
-        nat.check(L.flamed_fac_decode(self.handle, nat.ptr(bufs["x"]), nat.ptr(bufs["s"]), B, T, nat.ptr(bufs["wav"]),
-                                      nat.ptr(ws), ws.numel(), int(bool(self.dec.hip_graph)), nat.stream_ptr(dev)),
-                  "flamed_fac_decode")
+        if lens is not None:
+            nat.check(L.flamed_fac_decode_lens(self.handle, nat.ptr(bufs["x"]), nat.ptr(bufs["s"]), B, T,
+                                               (ctypes.c_int * B)(*lens), nat.ptr(bufs["wav"]), nat.ptr(ws), ws.numel(),
+                                               int(bool(self.dec.hip_graph)), nat.stream_ptr(dev)),
+                      "flamed_fac_decode_lens")
+        else:
+            nat.check(L.flamed_fac_decode(self.handle, nat.ptr(bufs["x"]), nat.ptr(bufs["s"]), B, T, nat.ptr(bufs["wav"]),
+                                          nat.ptr(ws), ws.numel(), int(bool(self.dec.hip_graph)), nat.stream_ptr(dev)),
+                      "flamed_fac_decode")
         return bufs["wav"].clone()
 
 

@@ -123,7 +123,10 @@ class Flamed(nn.Module):
                      solver_denoiser: str = "euler", exact_lengths: bool = False):
         """reference :168-217; solver_denoiser as in sample.  exact_lengths (opt-in): every utterance of the padded
         batch gets the latents it would get alone -- its condition fold and its solve run over its own frames only
-        and its padding frames are 0 (ProbGenerator.sample); the FaCodec decode is unchanged."""
+        and its padding frames are 0 (ProbGenerator.sample), and the FaCodec decode gets lens = (~tgt_mask).sum(-1), so
+        wav[u, :, :wav_lens[u]] is the waveform utterance u would get alone and wav[u, :, wav_lens[u]:] is exactly 0
+        (FACodecDecoder.inference(..., lens)).  outputs["wav_lens"] (samples, hop * len_u; with a codec_decoder and the
+        flag only) tells where each waveform ends; without the flag there is no such key and wav is as before."""
         start = time.time()
         dev = self.device
         phonemes, src_lens, prompts, timbres = phonemes.to(dev), src_lens.to(dev), prompts.to(dev), timbres.to(dev)
@@ -140,7 +143,11 @@ class Flamed(nn.Module):
                 den._hip.settle(block=False)
         outputs = {"prior_embs": prior_emb_cond, "prior_logits": prior_logits, "tgt_mask": tgt_mask,
                    "latents": latents, "time": time.time() - start}
-        if codec_decoder is not None:
+        if codec_decoder is not None and exact_lengths:
+            lens = (~tgt_mask).sum(-1)
+            outputs["wav"] = codec_decoder.inference(latents, timbres, lens=lens)
+            outputs["wav_lens"] = lens * (outputs["wav"].shape[-1] // latents.shape[-1])
+        elif codec_decoder is not None:
             outputs["wav"] = codec_decoder.inference(latents, timbres)
         return outputs
 

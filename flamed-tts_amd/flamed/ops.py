@@ -19,6 +19,8 @@ take tensors and scalars only); the registry holds weak references, so a dropped
   flamed_hip::pva_flow(id, x, mask, dur, sil, ts, nfe)  PVA.sample Euler loops       pva.py:97-109
   flamed_hip::length_regulate(x, pd, sd, lens, max_len, log_domain)  LengthRegulator.LR  pva.py:125-166
   flamed_hip::fac_decode(id, x, spk)               FACodecDecoder.inference        facodec.py:630-638
+  flamed_hip::fac_decode_lens(id, x, spk, lens)    exact lengths (no reference counterpart): every utterance of the
+                                                   padded batch decoded over its own frames, as if alone; 0 behind it
   flamed_hip::enc_encode(id, x)                    FACodecEncoder.forward          facodec.py:158-243
   flamed_hip::vq_encode(id, x)                     FACodecDecoder.forward(vq=True) facodec.py:470-533
   flamed_hip::prior_encode(id, texts, mask)        Encoder.forward (prior)         prior_generator.py:152-153
@@ -173,6 +175,17 @@ def _(oid, x, spk):
     return x.new_empty((B, 1, owner(oid).dec.hop_length * T), dtype=torch.float32)
 
 
+@torch.library.custom_op("flamed_hip::fac_decode_lens", mutates_args=())
+def fac_decode_lens(oid: int, x: Tensor, spk: Tensor, lens: List[int]) -> Tensor:
+    return owner(oid).decode(x, spk, lens=lens)
+
+
+@fac_decode_lens.register_fake
+def _(oid, x, spk, lens):
+    B, _, T = x.shape
+    return x.new_empty((B, 1, owner(oid).dec.hop_length * T), dtype=torch.float32)
+
+
 @torch.library.custom_op("flamed_hip::enc_encode", mutates_args=())
 def enc_encode(oid: int, x: Tensor) -> Tensor:
     return owner(oid).encode(x)
@@ -226,4 +239,4 @@ def _(oid, x, tgt_mask, prompts, prompts_len):
 
 
 OPS = ("den_velocity", "den_solve", "den_solve_rk2", "den_solve_lens", "den_solve_rk2_lens", "cond_fold", "cond_fold_exact",
-       "pva_flow", "length_regulate", "fac_decode", "enc_encode", "vq_encode", "prior_encode", "prior_decode")
+       "pva_flow", "length_regulate", "fac_decode", "fac_decode_lens", "enc_encode", "vq_encode", "prior_encode", "prior_decode")

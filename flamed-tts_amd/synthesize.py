@@ -225,7 +225,8 @@ def synthesize_with_metadata(model: Flamed, codec_encoder, codec_decoder, metada
                              exact_lengths: bool = False):
     """Batched `Flamed.sample_batch` over a `target|prompt|text` file (reference :220-303).  A denoiser solver
     other than Euler is appended to the target directory's name, and `-exact` for exact lengths (every utterance of
-    a padded batch then gets the latents it would get alone)."""
+    a padded batch then gets the latents and the waveform it would get alone, and its file is trimmed to its own
+    length, out["wav_lens"]; without the flag every file of a batch has the batch's padded length)."""
     with open(metadata_file, "r", encoding="utf-8") as fin:
         entries = [line.strip() for line in fin if line.strip()]
     target_dir = os.path.join(output_dir, f"nfe{nsteps_denoiser}-temp{temp_denoiser}{_solver_suffix(solver_denoiser, exact_lengths)}")
@@ -258,8 +259,9 @@ def synthesize_with_metadata(model: Flamed, codec_encoder, codec_decoder, metada
                                  nsteps_durgen=nsteps_durgen, nsteps_denoiser=nsteps_denoiser,
                                  solver_denoiser=solver_denoiser, exact_lengths=exact_lengths)
         per_sample = out["time"] / len(batch)
-        for item, wav_t in zip(batch, out["wav"]):
-            wav = wav_t[0].detach().cpu().numpy()
+        wav_lens = out["wav_lens"].tolist() if "wav_lens" in out else [None] * len(batch)
+        for item, wav_t, n in zip(batch, out["wav"], wav_lens):
+            wav = wav_t[0, :n].detach().cpu().numpy()
             write_wav(item["out_path"], wav, SR)
             meter.add(per_sample, len(wav))
     return meter.rtf()
@@ -307,8 +309,9 @@ def build_arg_parser():
                    help="Denoiser ODE solver; midpoint / heun are second order and --nsteps-denoiser (even) then "
                         "counts velocity evaluations.")
     p.add_argument("--exact-lengths", type=str2bool, default=False,
-                   help="Fold and solve every utterance of a padded batch over its own frames only, so its latents do "
-                        "not depend on the batch it shares (default: False, the reference's padded batch).")
+                   help="Fold, solve and decode every utterance of a padded batch over its own frames only, so its "
+                        "latents and its waveform do not depend on the batch it shares, and write each file of "
+                        "--metadata-file mode trimmed to its own length (default: False, the reference's padded batch).")
     p.add_argument("--temp-durgen", type=float, default=0.3, help="Duration generator temperature.")
     p.add_argument("--temp-denoiser", type=float, default=0.3, help="Denoiser temperature.")
     p.add_argument("--device", type=str, default="cuda:0", help="Device to run inference on.")

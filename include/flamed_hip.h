@@ -368,9 +368,22 @@ FLAMED_API int flamed_fac_num_weights(flamed_fac_t h);
 FLAMED_API int flamed_fac_load(flamed_fac_t h, const float* const* weights, int n_weights, hipStream_t stream);
 FLAMED_API size_t flamed_fac_workspace_size(flamed_fac_t h, int B, int T);
 /* latents: (B, in_channels, T) channels-first as the reference passes them; spk: (B, in_channels);
- * wav: (B, hop*T) with hop = prod(up_ratios).  use_graph != 0 replays a cached hipGraph. */
+ * wav: (B, hop*T) with hop = prod(up_ratios).  use_graph != 0 replays a cached hipGraph.  Every utterance is decoded
+ * over all T frames: in a padded ragged batch the last ~14 frames of a shorter utterance and everything behind them
+ * depend on its padding (flamed_fac_decode_lens below decodes each utterance over its own frames). */
 FLAMED_API int flamed_fac_decode(flamed_fac_t h, const float* latents, const float* spk, int B, int T, float* wav,
                                  void* ws, size_t ws_bytes, int use_graph, hipStream_t stream);
+/* Exact lengths: the same decode for a padded ragged batch.  lens: B HOST ints, 1 <= lens[u] <= T (read before the
+ * call returns).  Utterance u is decoded over its own lens[u] frames exactly as if it were alone at T = lens[u]: every
+ * replicate pad, zero pad and conv-transpose edge sits at its own end.  wav[u, : hop*lens[u]] is that waveform and
+ * wav[u, hop*lens[u] :] is written as 0; nothing stored in latents[u, :, lens[u]:] is read (NaN and inf included).
+ * Every length equal to T is flamed_fac_decode itself (same kernels, same graph, bitwise).  The ragged call keeps a
+ * hipGraph of its own, which holds no length: the lengths go to a handle-owned device array in stream order ahead of
+ * the replay, so one capture serves every ragged call of the same pointers and (B, T).  Workspace as for
+ * flamed_fac_decode; one call at a time per handle, as there.  A null pointer or a length outside 1..T returns 1001
+ * with a flamed_last_error text before any pointer is touched. */
+FLAMED_API int flamed_fac_decode_lens(flamed_fac_t h, const float* latents, const float* spk, int B, int T, const int* lens,
+                                      float* wav, void* ws, size_t ws_bytes, int use_graph, hipStream_t stream);
 
 /* ============================ FaCodec encoder (prompt encoding) ============================
  * Replaces FACodecEncoder.forward (facodec.py:183-216; EncoderBlock :136-155), SURVEY.md §8(f) f3.
