@@ -214,7 +214,10 @@ struct Tune {
                            // A/B bits: 1 = four-wave weight DMA (round 3
                            // default; since round 5 waves 1..3 issue, so wave 0's poll never waits behind weight loads:
                            // 21.50 -> 21.18 ms), 16384 blocking seals (+12 %),
-                           // 1024 2 x 2 wave split, 4096 drain behind the DMA.  Removed after measuring: the GEMM
+                           // 1024 2 x 2 wave split, 4096 drain behind the DMA, 2097152 selects the old row-major
+                           // LayerNorm row partials (default: tile-major, persist.hpp xpart_off: B = 1 T = 400
+                           // 20,846 -> 21,838 latent frames/s, profiles/rowpart_tiles_ab.txt);
+                           // 1048576 is unused.  Removed after measuring: the GEMM
                            // phases' deferred seal loads issued after the GEMM (r06ap neutral as a bit, but its code
                            // slowed the default kernel 2-5 %, r06ar)
   int pva_split = 0;       // PVA nets: split-K of their small-M fp32 GEMMs (fixed slice order); measured

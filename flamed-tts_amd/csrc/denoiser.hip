@@ -2547,8 +2547,8 @@ static size_t persist_layout(char* base, pk::Params* P) {
   char* ctr = take(4 * (size_t)pk::kCtrInts);
   char* sticky = take(4 * (size_t)pk::kStickyInts);
   char* seal = take((size_t)pk::kWGs * 16);
-  char* xp0 = take(T * pk::kSlots * 8);
-  char* xp1 = take(T * pk::kSlots * 8);
+  char* xp0 = take(pk::kXpartBytes);  // addressed by (group, row in group), not by T (persist.hpp xpart_off)
+  char* xp1 = take(pk::kXpartBytes);
   char* ximg = take(T * H * 4);
   char* a2 = take(T * H * 2);
   char* u = take(T * H * 2);

@@ -69,7 +69,7 @@ __device__ __forceinline__ int opq(int v) {
 // utterances (its modulation row, GroupNorm statistics and zero padding are its utterance's).
 // Exact lengths (the ragged variants): the utterance's rows still start at u T, but it holds Lu <= T frames and its
 // groups split those (Lu = T is the dense split).
-__device__ __forceinline__ void group_rows(int g, int T, int Lu, int B, int& r0, int& nr, int opt) {
+__host__ __device__ __forceinline__ void group_rows(int g, int T, int Lu, int B, int& r0, int& nr, int opt) {
   const int gpu = kGroups / B, u = g / gpu, gi = g - u * gpu;
   if (opt & 2) {  // whole 16-row tiles [gi MT / gpu, (gi + 1) MT / gpu) of the utterance
     const int MT = (Lu + 15) >> 4;
@@ -590,7 +590,10 @@ __device__ __forceinline__ void gemm_kh(const bf16* A, int r0, int nr, char* wl,
 // LayerNorm partials (mean, M2 over the slot's 32 columns) of row 16 tile + c, from the transposed accumulator
 // layout (lane (c, q): columns 16 nt + 4 q + r): 8 values per lane, summed over the row's four q lanes (c, c + 16,
 // c + 32, c + 48; ((s0 + s1) + (s2 + s3)) in every lane, by commutativity), two passes; write-through 8-B store.
-__device__ __forceinline__ void store_partials_t(float2* xpart, const float (&x)[2][4], int r0, int nr, int s, int tile, int lane_in) {
+// Tile-major (tm, the default; persist.hpp xpart_off): the 16 lanes (c, 0) of the wave fill one 128-B line, which no
+// other workgroup writes; row-major (persist_opt 2097152): cell [row][slot].
+__device__ __forceinline__ void store_partials_t(float2* xpart, const float (&x)[2][4], int r0, int nr, int s, int tile, int lane_in,
+                                                 int g, bool tm) {
   const int lane = opq(lane_in);
   const int c = lane & 15, q = lane >> 4;
   float sm = ((x[0][0] + x[0][1]) + (x[0][2] + x[0][3])) + ((x[1][0] + x[1][1]) + (x[1][2] + x[1][3]));
@@ -608,9 +611,12 @@ __device__ __forceinline__ void store_partials_t(float2* xpart, const float (&x)
   m2 += __shfl_xor(m2, 16);
   m2 += __shfl_xor(m2, 32);
   const int row = 16 * tile + c;
-  if (q == 0 && row < nr)
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(xpart + (size_t)(r0 + row) * kSlots + s),
+  if (q == 0 && row < nr) {
+    float2* const cell = tm ? reinterpret_cast<float2*>(reinterpret_cast<char*>(xpart) + xpart_off(g, row, s))
+                            : xpart + (size_t)(r0 + row) * kSlots + s;
+    __hip_atomic_store(reinterpret_cast<unsigned long long*>(cell),
                        __builtin_bit_cast(unsigned long long, make_float2(mean, m2)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
 }
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -709,17 +715,37 @@ __device__ __forceinline__ void unpack_row_partials(const u32x4 (&v)[8], float (
   }
 }
 
+// 16 consecutive slots' partials of one row from the tile-major image (persist.hpp xpart_off; `base` = the offset of
+// the first, slot stride 128 B): sixteen 8-B sc1 loads, packed as the row-major image's eight 16-B loads deliver them
+// (slots 2 k and 2 k + 1 in v[k]), so unpack_row_partials and the combine order are the same for both layouts.
+__device__ __forceinline__ void ld_partials_tm(u32x4 (&v)[8], __amdgpu_buffer_rsrc_t rs, unsigned base) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const u32x2 lo = __builtin_amdgcn_raw_buffer_load_b64(rs, base + 256 * k, 0, 16);
+    const u32x2 hi = __builtin_amdgcn_raw_buffer_load_b64(rs, base + 256 * k + 128, 0, 16);
+    v[k] = u32x4{lo.x, lo.y, hi.x, hi.y};
+  }
+}
+
 // (mean, rstd) of rows [ra, rb) from the 32 slots' partials (sc1 loads), into st[2 (r - rbase)]; two
-// adjacent lanes per row (16 partials each).
-__device__ __forceinline__ void row_stats(const float2* xpart, int T, int ra, int rb, int rbase, float* st) {
+// adjacent lanes per row (16 partials each).  Tile-major (tm): tm_base(it, row, half) gives the offset of the row's
+// cell of slot 16 half in trip `it` of the thread's loop -- the callers know it without arithmetic here (the group's own
+// rows) or have worked it out once per launch (the depthwise window, whose halo rows lie in other groups' tiles).
+template <class TmBase>
+__device__ __forceinline__ void row_stats(const float2* xpart, int T, int ra, int rb, int rbase, float* st, bool tm, TmBase tm_base) {
   const int n2 = 2 * (rb - ra);
-  const __amdgpu_buffer_rsrc_t rs = rsrc(xpart, (unsigned)T * kSlots * 8);
-  for (int idx = opq(threadIdx.x); idx < ((n2 + 63) & ~63); idx += kThreads) {
+  const __amdgpu_buffer_rsrc_t rs = rsrc(xpart, tm ? kXpartBytes : (unsigned)T * kSlots * 8);
+  int it = 0;
+  for (int idx = opq(threadIdx.x); idx < ((n2 + 63) & ~63); idx += kThreads, ++it) {
     const bool act = idx < n2;
     const int row = ra + (act ? idx >> 1 : 0), half = idx & 1;
     u32x4 v[8];
+    if (tm) {
+      ld_partials_tm(v, rs, tm_base(it, row, half));
+    } else {
 #pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = ld16(rs, (unsigned)((row * kSlots + half * 16 + 2 * k) * 8));
+      for (int k = 0; k < 8; ++k) v[k] = ld16(rs, (unsigned)((row * kSlots + half * 16 + 2 * k) * 8));
+    }
     float mv[16], qv[16];
     unpack_row_partials(v, mv, qv);
     const float2 ms = combine_row_partials(mv, qv, [](float x) { return dpp_add<kDppXor1>(x); });
@@ -735,11 +761,16 @@ __device__ __forceinline__ void row_stats(const float2* xpart, int T, int ra, in
 // (c, 1) each load 16 of their row's 32 partials (sc1, to registers; every other lane and rows >= nr load from past
 // the buffer range: zeros, no memory traffic) ...
 __device__ __forceinline__ void load_row_partials(u32x4 (&v)[8], const float2* xpart, int T, int r0, int nr, int tile,
-                                                  int lane_in) {
+                                                  int lane_in, int g, bool tm) {
   const int lane = opq(lane_in);
   const int c = lane & 15, q = lane >> 4, row = 16 * tile + c;
+  const bool on = q < 2 && row < nr;
+  if (tm) {  // the group's own rows: (g, row) directly
+    ld_partials_tm(v, rsrc(xpart, kXpartBytes), on ? xpart_off(g, row, q * 16) : 0x7ff00000u);
+    return;
+  }
   const __amdgpu_buffer_rsrc_t rs = rsrc(xpart, (unsigned)T * kSlots * 8);
-  const unsigned base = q < 2 && row < nr ? (unsigned)(((r0 + row) * kSlots + q * 16) * 8) : 0x7ff00000u;
+  const unsigned base = on ? (unsigned)(((r0 + row) * kSlots + q * 16) * 8) : 0x7ff00000u;
 #pragma unroll
   for (int k = 0; k < 8; ++k) v[k] = ld16(rs, base + 16 * k);
 }
@@ -847,6 +878,16 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
   // 2 x 2 wave-split variant keeps the LDS table (with the eight loads held across gemm_kh it spills)
   constexpr bool kDefer = NTW == 1 && !KH;
   const bool gran = (P.opt & 512) != 0;       // GroupNorm partials as tagged granules (gnp zeroed per launch)
+  // LayerNorm row partials tile-major (xpart_off; persist_opt 2097152: row-major), at every chunk count.  The five-chunk
+  // variant's time moves with the build more than with the layout (T = 2400 nfe 256, ms, parent | tile-major: 105.67
+  // 105.75 | 106.06 106.36, 105.18 | 105.49, 105.51 105.65 | 105.58 105.69 on the first build, 105.30-106.14 | 103.08-
+  // 104.35 over five runs on the final one), and keeping it row-major by a constexpr choice measured worse than either:
+  // 105.85-106.02 | 109.36-110.58 (151 spilled VGPRs; its allocation shifts with any change of the source).  The
+  // other counts, parent -> this: one chunk 18.8 -> 17.9 ms, two 25.1 -> 24.5, three 35.0 -> 32.9, four 41.9 -> 40.6,
+  // six T = 3000 nfe 256 127.7 -> 124.4, seven T = 3500 76.4 -> 74.0 and B = 4 T = 800 75.1 -> 72.3, eight T = 4000
+  // 85.5 -> 80.4 (profiles/rowpart_tiles_ab.txt).
+  constexpr bool kTileMajor = true;
+  const bool tm = kTileMajor && !(P.opt & 2097152);
   const int gpu = kGroups / P.B, utt = g / gpu;  // this group's utterance and its frames [ub, ue)
   // frames of group k's utterance (exact lengths: its own count; rows [ue, ub + T) then belong to nobody)
   auto len_of = [&](int k) {
@@ -1107,6 +1148,43 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
 
   float X[NTW][2][4];  // residual stream tiles (this wave's tiles wave + 4 i: 16 rows x 32 columns each), MFMA layout
 
+  // Tile-major row partials of the depthwise window [wa, wz) (the utterance's frames within kHalo of the group): a
+  // halo row's cell is found through the group that owns the row (row_owner: two integer divisions).  The thread's rows
+  // are the same in every phase and step, so up to two chunks per group the offsets of its row_stats trips are found
+  // once here and kept in registers: with the divisions inside the step loop the one-chunk Euler variant went from 0
+  // to 36 B of scratch per lane.  From three chunks on the variants spill already and registers held across the whole
+  // solve cost more than the divisions (four chunks, Euler: 97 -> 135 spilled VGPRs with the offsets kept, B = 4
+  // T = 400 41.6-41.8 ms (parent) -> 42.6-42.9, against 42.1 -> 40.6-40.7 with the divisions in the loop; six chunks
+  // T = 3000 nfe 256 127.1-127.9 -> 126.8-127.3 against 127.6 -> 123.4-123.9): they look the owner up where they read.
+  constexpr bool kHoist = NTW <= 2;
+  constexpr int kWinIt = kHoist ? (2 * (kChunk * NTW + 2 * kHalo) + kThreads - 1) / kThreads : 1;
+  [[maybe_unused]] unsigned wbase[kWinIt];
+  if constexpr (kHoist) {
+    // (the same [wa, wz) and the same thread -> row map as the depthwise phase's row_stats call below: trip `it` of
+    // thread tid handles idx = tid + kThreads it, row wa + idx / 2, half idx & 1 -- change them together)
+    const int wa = max(r0 - kHalo, ub), wz = min(r0 + nr + kHalo, ue), n2 = 2 * (wz - wa);
+#pragma unroll
+    for (int it = 0; it < kWinIt; ++it) {
+      const int idx = tid + kThreads * it;
+      int gi = 0, lrow = 0;
+      if (tm && idx < n2) row_owner(wa + (idx >> 1) - ub, Tu, gpu, P.opt, gi, lrow);
+      wbase[it] = xpart_off(utt * gpu + gi, lrow, (idx & 1) * 16);
+    }
+  }
+  auto win_base = [&](int it, int row, int half) {
+    if constexpr (kHoist) {
+      unsigned b = wbase[0];
+#pragma unroll
+      for (int k = 1; k < kWinIt; ++k) b = it == k ? wbase[k] : b;
+      return b;
+    } else {
+      int gi, lrow;
+      row_owner(row - ub, Tu, gpu, P.opt, gi, lrow);
+      return xpart_off(utt * gpu + gi, lrow, half * 16);
+    }
+  };
+  auto own_base = [&](int, int row, int half) { return xpart_off(g, row - r0, half * 16); };
+
   for (int step = P.s0; step < P.s1; ++step) {
     const float* md = P.mods + (size_t)(step * MB + mutt) * P.MS;  // this utterance's modulation row
     cur_step = step;
@@ -1139,7 +1217,7 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) X[ci][nt][i] += binv[nt][i];
       if (16 * tl < nr) {
-        store_partials_t(P.xpart[0], X[ci], r0, nr, s, tl, lane);
+        store_partials_t(P.xpart[0], X[ci], r0, nr, s, tl, lane, g, tm);
         store_halo_t(P.ximg, X[ci], r0, nr, col0, tl, TT, lane);
       }
     }
@@ -1241,7 +1319,8 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
           ova[nt][r] = fin ? sc1 : olw[nt][r] * sc1;
           ovb[nt][r] = fin ? osh[nt][r] : olb[nt][r] * sc1 + osh[nt][r];
         }
-      const int wa = max(r0 - kHalo, ub), wz = min(r0 + nr + kHalo, ue);  // the utterance's frames only
+      // the utterance's frames only (wbase above was worked out for exactly this window)
+      const int wa = max(r0 - kHalo, ub), wz = min(r0 + nr + kHalo, ue);
       // Everything this phase reads that does not wait on another phase goes out first, so the loads'
       // latencies overlap: the thread's halo item (its 4 columns col0 + 4 (tid & 7)), their modulation vectors,
       // the depthwise taps of channel cc, the row statistics.  Halo items: the group's kHalo rows above and
@@ -1253,7 +1332,7 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
         const int r = r0 - kHalo + hp;
         if (hid < 2 * kHalo && r >= ub && r < ue) hv = as_f4(ld16(rx, (unsigned)(((size_t)r * H + col0 + 4 * (tid & 7)) * 4)));
       }
-      row_stats(P.xpart[0], TT, wa, wz, r0 - kHalo, st);
+      row_stats(P.xpart[0], TT, wa, wz, r0 - kHalo, st, tm, win_base);
       __syncthreads();
       PST(step);  // halo rows + row statistics in
       // per chunk: window hs[pw] = frame r0 + c0 - kHalo + pw (pw < kWin): own rows from X (registers), halo rows
@@ -1540,7 +1619,7 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
           }
         }
         if (16 * tl < nr) {
-          store_partials_t(P.xpart[1], X[ci], r0, nr, s, tl, lane);
+          store_partials_t(P.xpart[1], X[ci], r0, nr, s, tl, lane, g, tm);
           store_op_t(P.xa, g, s, tl, v, r0, nr, col0, TT, lane, frag);
         }
       }
@@ -1571,8 +1650,8 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
       // LDS table before the GEMM (issued between the GEMM's A loads and their wait instead, r06j measured 20.84 vs
       // 20.63 ms per B = 1 solve: slower)
       [[maybe_unused]] u32x4 rp_m0[8];
-      if constexpr (kDefer) load_row_partials(rp_m0, P.xpart[1], TT, r0, nr, wave, lane);
-      else row_stats(P.xpart[1], TT, r0, r0 + nr, r0 - kHalo, st);
+      if constexpr (kDefer) load_row_partials(rp_m0, P.xpart[1], TT, r0, nr, wave, lane, g, tm);
+      else row_stats(P.xpart[1], TT, r0, r0 + nr, r0 - kHalo, st, tm, own_base);
       f32x4 accm_m0[NTW][2];  // every tile's products (several chunks: one streamed pass, epilogues after it)
       if constexpr (KH) gemm_kh<kH>(P.xa, r0, nr, (smem + wb * kWPanel), accm_m0[0], wave, lane, PSTP(step), g, frag);
       else if constexpr (NTW == 1) gemm<kH>(P.xa, r0, nr, (smem + wb * kWPanel), accm_m0[0], wave, lane, PSTP(step), g, frag);
@@ -1632,7 +1711,7 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) X[ci][nt][i] = X[ci][nt][i] + g2v[nt][i] * (acc[nt][i] + bm2[nt][i]);
         if (16 * tl < nr) {
-          store_partials_t(P.xpart[0], X[ci], r0, nr, s, tl, lane);
+          store_partials_t(P.xpart[0], X[ci], r0, nr, s, tl, lane, g, tm);
           store_halo_t(P.ximg, X[ci], r0, nr, col0, tl, TT, lane);
         }
       }
@@ -1667,8 +1746,8 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
     if (!wait_ge(errw, fails, tmo, mygrp, 0, 1, 32 * L, flag) || !seal_wait(g, 1)) { fail_exit(); return; }
     PST(step);
     [[maybe_unused]] u32x4 rp_out[8];  // row statistics as in mlp.0: loads here, the combine after the MFMA loop
-    if constexpr (kDefer) load_row_partials(rp_out, P.xpart[1], TT, r0, nr, wave, lane);
-    else row_stats(P.xpart[1], TT, r0, r0 + nr, r0 - kHalo, st);
+    if constexpr (kDefer) load_row_partials(rp_out, P.xpart[1], TT, r0, nr, wave, lane, g, tm);
+    else row_stats(P.xpart[1], TT, r0, r0 + nr, r0 - kHalo, st, tm, own_base);
     f32x4 acco[NTW][2];  // every tile's products first: with several chunks Y goes into this phase's panel buffer
     if constexpr (KH) gemm_kh<kH>(P.xa, r0, nr, (smem + wb * kWPanel), acco[0], wave, lane, PSTP(step), g, frag);
     else if constexpr (NTW == 1) gemm<kH>(P.xa, r0, nr, (smem + wb * kWPanel), acco[0], wave, lane, PSTP(step), g, frag);
@@ -1945,6 +2024,30 @@ int persist_launch(const Params& Pin, hipStream_t st, bool cooperative, bool rag
 extern "C" FLAMED_API int flamed_persist_stamps(void* buf, int step) { return fl::pk::persist_stamps(buf, step); }
 extern "C" FLAMED_API int flamed_persist_gndump(void* buf, int step) { return fl::pk::persist_gndump(buf, step); }
 #endif
+
+// Host-side view of the tile-major row-partial addressing (include/flamed_diag.h; CPU unit test): group g's row lrow
+// and slot s under the row partition of (B, T, lens, opt).
+extern "C" FLAMED_API int flamed_persist_rowpart(int B, int T, const int* lens, int opt, int g, int lrow, int s, int* row,
+                                                 long long* off, int* owner_g, int* owner_lrow) {
+  using namespace fl::pk;
+  if (!row || !off || !owner_g || !owner_lrow) return fl::kBadArg;
+  if ((B != 1 && B != 2 && B != 4 && B != 8) || T < 1 || g < 0 || g >= kGroups || s < 0 || s >= kSlots || lrow < 0) return fl::kBadArg;
+  const int gpu = kGroups / B, u = g / gpu, Lu = lens ? lens[u] : T;
+  if (Lu < 1 || Lu > T) return fl::kBadArg;
+  int r0, nr;
+  group_rows(g, T, Lu, B, r0, nr, opt);
+  *row = -1;
+  *off = -1;
+  *owner_g = *owner_lrow = -1;
+  if (lrow >= nr || lrow >= kMaxRows) return fl::kOk;  // past the group's end: nowhere
+  *row = r0 + lrow;
+  *off = (long long)xpart_off(g, lrow, s);
+  int gi, ol;
+  row_owner(*row - u * T, Lu, gpu, opt, gi, ol);
+  *owner_g = u * gpu + gi;
+  *owner_lrow = ol;
+  return fl::kOk;
+}
 
 // Host-side check of the reset prologue's ticket arithmetic (include/flamed_diag.h; CPU unit test).
 extern "C" FLAMED_API int flamed_persist_ticket(unsigned ticket, unsigned cur, unsigned* target, int* reached) {

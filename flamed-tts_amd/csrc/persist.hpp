@@ -84,6 +84,32 @@ __host__ __device__ inline unsigned arrive_target(unsigned ticket) {
 }
 __host__ __device__ inline bool arrive_reached(unsigned cur, unsigned target) { return (int)(cur - target) >= 0; }
 
+// LayerNorm row partials (Params::xpart), tile-major: [group][16-row tile of the group][slot][row in tile] float2, so
+// the 16 rows a wave stores for one (tile, slot) are one 128-B line with a single writer (row-major, a row's 32 slots
+// share two lines written 8 B at a time by 16 workgroups on 4 XCDs each).  A row is addressed as the fragment images
+// are, by its group and its index in the group (group_rows); byte offset of (group g, row lrow of it, slot s):
+constexpr int kGroupTiles = kMaxRows / 16;
+constexpr unsigned kXpartBytes = (unsigned)kGroups * kGroupTiles * kSlots * 128u;
+// (the row-major image, kMaxT rows of kSlots cells, fits the same buffer: the persistent layout allocates kXpartBytes)
+static_assert(kXpartBytes >= (unsigned)kMaxT * kSlots * 8u, "row partial buffers");
+__host__ __device__ inline unsigned xpart_off(int g, int lrow, int s) {
+  return (unsigned)((((g * kGroupTiles + (lrow >> 4)) * kSlots + s) * 16 + (lrow & 15)) * 8);
+}
+// The group that owns frame i < Lu of an utterance (gi of its gpu = 8 / B groups) and the frame's index in that group:
+// the inverse of group_rows (persist.hip), for a reader of another group's rows (the depthwise halo).  opt bit 2:
+// whole 16-row tiles, group gi holding tiles [gi MT / gpu, (gi + 1) MT / gpu) -- the last gi with gi MT / gpu <= i / 16.
+__host__ __device__ inline void row_owner(int i, int Lu, int gpu, int opt, int& gi, int& lrow) {
+  if (opt & 2) {
+    const int MT = (Lu + 15) >> 4;
+    gi = (((i >> 4) + 1) * gpu - 1) / MT;
+    lrow = i - 16 * (gi * MT / gpu);
+    return;
+  }
+  const int R = (Lu + gpu - 1) / gpu;
+  gi = i / R;
+  lrow = i - gi * R;
+}
+
 struct BlockW {
   const bf16 *w2, *w3, *m0, *m2;
   const float *b2, *b3, *mb0, *mb2, *lnw, *lnb, *lnmw, *lnmb, *dww, *dwb, *gnw, *gnb;  // dww: tap-major (31, H)
@@ -104,7 +130,8 @@ struct Params {
   const bf16* wout;        // conv_out taps stacked (3 C) x H
   const float* bout;
   float* xt;               // Euler state (T x C), read at launch start, written at the end
-  float2* xpart[2];        // LayerNorm row partials (mean, M2) over each slot's 32 columns: T x 32; [0]
+  float2* xpart[2];        // LayerNorm row partials (mean, M2) over each slot's 32 columns, tile-major (xpart_off;
+                           // persist_opt 2097152: row-major, T x 32); [0]
                            // from proj_in / mlp.2 (read by the next dwconv phase of EVERY group: halo
                            // rows), [1] from conv_3 (read by mlp.0 / conv_out of the same group) -- two
                            // buffers, so a group's conv_3 never overwrites what a slower neighbour's

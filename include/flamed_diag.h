@@ -75,6 +75,13 @@ FLAMED_API int flamed_den_ws_offsets(flamed_den_t h, int B, int T, size_t* off);
  * completes the launch of `ticket` (a fetch_add result), and whether counter value `cur` has reached it
  * (wrap-safe across 2^32). */
 FLAMED_API int flamed_persist_ticket(unsigned ticket, unsigned cur, unsigned* target, int* reached);
+/* The persistent solve's tile-major LayerNorm row partials, host-side (no GPU): for B utterances of T frames (lens:
+ * B exact lengths, or NULL), row partition `opt` (persist_opt; bit 2), group g < 8, row lrow of that group and slot
+ * s < 32: the frame `*row` (row index in the B x T batch) and the byte offset `*off` of its (mean, M2) cell in the
+ * partial buffer, both -1 when lrow lies past the group's end; `*owner_g` / `*owner_lrow` give the (group, row in group)
+ * that a reader of frame `*row` derives (the depthwise halo reads other groups' rows that way). */
+FLAMED_API int flamed_persist_rowpart(int B, int T, const int* lens, int opt, int g, int lrow, int s, int* row, long long* off,
+                                      int* owner_g, int* owner_lrow);
 /* Split-chain replay streams of this handle: how many the hardware-queue probe parked (they serialised with an
  * earlier chain's stream) and how many re-creations it took in total. */
 FLAMED_API int flamed_den_chain_info(flamed_den_t h, int* parked, int* retries);
