@@ -13,6 +13,7 @@
 // pva.py:111-112), builds the interleaved phone/silence repeat prefix sums, and gathers the frames.
 #include "flamed_hip.h"
 #include "gemm.hpp"
+#include "lens.hpp"
 #include "pvaflow.hpp"
 
 #include <mutex>
@@ -54,9 +55,26 @@ __global__ void split_proj_kernel(const float* __restrict__ src, float* __restri
   else we[(size_t)r * D + c - 1] = src[i];
 }
 
+// Exact lengths (flamed_pva_flow_exact): utterance u of the padded batch owns rows [u L, u L + lens[u]).  A conv
+// window is cut at that end instead of at L, and a row behind it gathers nothing; the dense loaders (EX = false)
+// carry no length and are the loaders they always were.
+template <bool EX>
+struct DurLens {
+  __device__ int len(int, int L) const { return L; }
+};
+template <>
+struct DurLens<true> {
+  const int* __restrict__ lens;  // B device ints (handle-owned, filled stream-ordered per call)
+  __device__ int len(int m, int L) const {
+    const int n = lens[m / L];
+    return n < 0 ? 0 : (n < L ? n : L);
+  }
+};
+
 // conv1 A operand: out0[src] = P[src] + w0 * xt[src] + temb (zero outside the utterance).  With a
 // device step counter `ctr` the time-embedding row is temb + (*ctr) * Cin (graph replay).
-struct LoadDurIn {
+template <bool EX>
+struct LoadDurInT : DurLens<EX> {
   const float* __restrict__ P;
   const float* __restrict__ w0;
   const float* __restrict__ xt;
@@ -70,8 +88,11 @@ struct LoadDurIn {
   __device__ Raw issue(int m, int k) const {
     Raw r;
     int tap = k / Cin, c = k - tap * Cin;
-    int l = m % L + tap - 1;
-    if (l < 0 || l >= L) {
+    const int lm = m % L, Lr = this->len(m, L);
+    int l = lm + tap - 1;
+    bool out = l < 0 || l >= Lr;
+    if constexpr (EX) out = out || lm >= Lr;
+    if (out) {
       r.v[0] = r.v[1] = r.v[2] = r.v[3] = 0.f;
       return r;
     }
@@ -87,12 +108,50 @@ struct LoadDurIn {
   }
   template <typename D> __device__ u32x4 finish(const Raw& r, int, int, const float*, int) const { return pack_chunk<D>(r.v); }
 };
+using LoadDurIn = LoadDurInT<false>;
+
+// conv2's A operand with exact lengths: LoadConvRows<float, true> (LayerNorm_1 of the tap rows), the window cut at the
+// end of the row's own utterance.
+struct LoadConvRowsLens {
+  LoadConvRows<float, true> base;
+  DurLens<true> dl;
+  using Raw = LoadConvRows<float, true>::Raw;
+  static constexpr int stat_rows(int BM) { return LoadConvRows<float, true>::stat_rows(BM); }
+  __device__ void prologue(int bm, int BM, int M, float* st) const { base.prologue(bm, BM, M, st); }
+  __device__ Raw issue(int m, int k) const {
+    const int L = base.L, lm = m % L, Lr = dl.len(m, L);
+    const int l = lm + (k / base.Cin - base.KT / 2) * base.dil;
+    if (lm >= Lr || l < 0 || l >= Lr) {
+      Raw r;
+      r.src = -1;
+      return r;
+    }
+    return base.issue(m, k);
+  }
+  template <typename D> __device__ u32x4 finish(const Raw& r, int m, int k, const float* st, int bm) const {
+    return base.template finish<D>(r, m, k, st, bm);
+  }
+};
+
+// the head's padding test: the mask byte (dense), or the row's place in its own utterance (exact lengths: a row
+// behind the end is written as 0 and never read)
+struct HeadMask {
+  const uint8_t* __restrict__ mask;
+  static constexpr bool kExact = false;
+  __device__ bool pad(int m) const { return mask[m] != 0; }
+};
+struct HeadLens {
+  DurLens<true> dl;
+  int L;
+  static constexpr bool kExact = true;
+  __device__ bool pad(int m) const { return m % L >= dl.len(m, L); }
+};
 
 // LN2 + Linear(F->1) + masked_fill(mask, 0) + Euler update; one wave per row.
-template <int F>
+template <int F, class MK>
 __global__ __launch_bounds__(256) void dur_head_kernel(const float* __restrict__ R2, const float* __restrict__ g,
                                                        const float* __restrict__ b, const float* __restrict__ wl,
-                                                       const float* __restrict__ bl, const uint8_t* __restrict__ mask,
+                                                       const float* __restrict__ bl, MK mask,
                                                        float* xt, int M, float dt, int* ctr) {
   constexpr int PER = F / 64;
   if (ctr && blockIdx.x == 0 && threadIdx.x == 0) *ctr += 1;  // end of an Euler step (sil net head)
@@ -123,8 +182,12 @@ __global__ __launch_bounds__(256) void dur_head_kernel(const float* __restrict__
   }
   dot = wave_sum64(dot);
   if (lane == 0) {
-    float vel = mask[m] ? 0.f : dot + bl[0];
-    xt[m] = __fadd_rn(xt[m], __fmul_rn(dt, vel));
+    if constexpr (MK::kExact) {
+      xt[m] = mask.pad(m) ? 0.f : __fadd_rn(xt[m], __fmul_rn(dt, dot + bl[0]));
+    } else {
+      float vel = mask.pad(m) ? 0.f : dot + bl[0];
+      xt[m] = __fadd_rn(xt[m], __fmul_rn(dt, vel));
+    }
   }
 }
 
@@ -153,6 +216,9 @@ struct DurNet {
   float *w0, *we, *c1w, *c2w;  // packed
   const float *pb, *t1w, *t1b, *t2w, *t2b, *c1b, *g1, *b1, *c2b, *g2, *b2, *lw, *lb;  // copies in the arena
   PvaGraph graph;   // the (duration, silence) pair's cached flow graph, kept on the duration net's handle
+  PvaGraph graph_x; // the exact-lengths flow's graph (flamed_pva_flow_exact): a cache of its own, so dense and exact
+                    // calls do not evict each other; its kernels read this call's lengths from xlens
+  DevLens xlens;
   // split-K of the net's small-M GEMMs (their K chains, 18 / 36 fp32 K-steps, are the step's latency):
   // per-handle slab + self-resetting tile counters, so the two nets' concurrent graph branches never share
   SplitCtx split;
@@ -222,18 +288,32 @@ struct NetBufs {
 };
 static int net_step(DurNet* n, const float* P, const float* temb, float* xt, const uint8_t* mask, int B, int L, float dt,
                     const NetBufs& w, hipStream_t st, const int* ctr = nullptr, int* ctr_inc = nullptr,
-                    bool split = true) {
+                    bool split = true, const int* lens = nullptr) {
   const int M = B * L, D = n->D, F = n->F;
   const int NT = F / 64;
   SplitScope split_scope(split && n->split_mem && tune_snapshot_pva_split() ? &n->split : nullptr);
   int rc;
-  if ((rc = launch_gemm_auto<float>(pick_cfg(M) == kCfgSmall ? kCfgSmall : kCfgMid, LoadDurIn{P, n->w0, xt, temb, D, L, ctr}, n->c1w, 3 * D,
+  if (lens) {  // exact lengths: the same three launches, windows and head cut at every utterance's own end
+    if ((rc = launch_gemm_auto<float>(pick_cfg(M) == kCfgSmall ? kCfgSmall : kCfgMid,
+                                      LoadDurInT<true>{{lens}, P, n->w0, xt, temb, D, L, ctr}, n->c1w, 3 * D,
+                                      EpiBiasStatsT<true>{n->c1b, w.R1, F, w.S1, NT}, M, F, 3 * D, st)))
+      return rc;
+    if ((rc = launch_gemm<float>(LoadConvRowsLens{{w.R1, F, L, 3, 1, w.S1, NT, 64, 1e-5f, n->g1, n->b1}, {lens}}, n->c2w, 3 * F,
+                                 EpiBiasAct<float, 3>{n->c2b, w.R2, F}, M, F, 3 * F, st)))
+      return rc;
+    hipLaunchKernelGGL((dur_head_kernel<384, HeadLens>), dim3((M + 3) / 4), dim3(256), 0, st, w.R2, n->g2, n->b2, n->lw, n->lb,
+                       HeadLens{{lens}, L}, xt, M, dt, ctr_inc);
+    FL_LAUNCH_CHECK();
+    return kOk;
+  }
+  if ((rc = launch_gemm_auto<float>(pick_cfg(M) == kCfgSmall ? kCfgSmall : kCfgMid, LoadDurIn{{}, P, n->w0, xt, temb, D, L, ctr}, n->c1w, 3 * D,
                                           EpiBiasStatsT<true>{n->c1b, w.R1, F, w.S1, NT}, M, F, 3 * D, st)))
     return rc;
   if ((rc = launch_gemm<float>(LoadConvRows<float, true>{w.R1, F, L, 3, 1, w.S1, NT, 64, 1e-5f, n->g1, n->b1}, n->c2w,
                                           3 * F, EpiBiasAct<float, 3>{n->c2b, w.R2, F}, M, F, 3 * F, st)))
     return rc;
-  hipLaunchKernelGGL(dur_head_kernel<384>, dim3((M + 3) / 4), dim3(256), 0, st, w.R2, n->g2, n->b2, n->lw, n->lb, mask, xt, M, dt, ctr_inc);
+  hipLaunchKernelGGL((dur_head_kernel<384, HeadMask>), dim3((M + 3) / 4), dim3(256), 0, st, w.R2, n->g2, n->b2, n->lw, n->lb,
+                     HeadMask{mask}, xt, M, dt, ctr_inc);
   FL_LAUNCH_CHECK();
   return kOk;
 }
@@ -309,7 +389,7 @@ static bool stream_capturing(hipStream_t st) {
 // *done = false: the runtime refused the cooperative grid (this row-group count never runs persistently on this
 // device); the caller runs the graph path.
 static int pva_persist_run(DurNet* nd, DurNet* ns, const PvaWs& w, const uint8_t* mask, float* dur_t, float* sil_t, int nfe,
-                           int B, int L, float dt, hipStream_t st, bool* done) {
+                           int B, int L, float dt, hipStream_t st, bool* done, const int* lens = nullptr) {
   *done = false;
   const int M = B * L;
   const bool cap = stream_capturing(st);
@@ -329,6 +409,7 @@ static int pva_persist_run(DurNet* nd, DurNet* ns, const PvaWs& w, const uint8_t
   pva_persist_layout(nd->pmem, nd->F, &P);
   P.M = M; P.L = L; P.MT = (M + 15) / 16; P.RG = pva_persist_groups(M, nd->F); P.nfe = nfe; P.dt = dt;
   P.mask = mask;
+  P.lens = lens;  // exact lengths: the EX kernels (the mask is then null and never read)
   const DurNet* nets[2] = {nd, ns};
   const float* Pn[2] = {w.Pd, w.Ps};
   const float* Tn[2] = {w.TEMBd, w.TEMBs};
@@ -365,6 +446,8 @@ static int pva_persist_run(DurNet* nd, DurNet* ns, const PvaWs& w, const uint8_t
 
 // -------- length regulator --------
 // One workgroup per utterance: repeats (interleaved phone/silence), exclusive prefix sum, total.
+// EX (flamed_lr_lengths_exact): a padded phoneme repeats 0 frames, so tgt_len is the length the utterance has alone.
+template <bool EX>
 __global__ __launch_bounds__(256) void lr_lengths_kernel(const float* __restrict__ pd, const float* __restrict__ sd,
                                                          const int64_t* __restrict__ src_lens, int L, int log_domain,
                                                          int64_t* __restrict__ cum, int64_t* __restrict__ tgt_len) {
@@ -378,6 +461,9 @@ __global__ __launch_bounds__(256) void lr_lengths_kernel(const float* __restrict
     float v = (j & 1) ? sd[(size_t)b * L + l] : pd[(size_t)b * L + l];
     if (log_domain) v = fmaxf(rintf(expf(v) - 1.0f), 0.0f);   // pva.py:111-112
     bool valid = l < sl;
+    if constexpr (EX) {
+      if (!valid) return 0;
+    }
     if (!(j & 1)) {
       int64_t r = valid ? (int64_t)rintf(v) : 0;              // pva.py:136-137 (round, clamp >= 1)
       return r < 1 ? 1 : r;
@@ -461,6 +547,8 @@ FLAMED_API int flamed_dur_destroy(flamed_dur_t h) {
     std::lock_guard<std::mutex> lk(n->mu);
     DeviceGuard dg(n->device);
     n->graph.release();
+    n->graph_x.release();
+    n->xlens.release();
     n->release_persist();
     if (n->dev) (void)hipFree(n->dev);
     if (n->split_mem) (void)hipFree(n->split_mem);
@@ -480,6 +568,8 @@ FLAMED_API int flamed_dur_load(flamed_dur_t h, const float* const* w, int nw, hi
   if (n->device >= 0 && n->device != wdev) {
     DeviceGuard og(n->device);
     n->graph.release();
+    n->graph_x.release();
+    n->xlens.release();
     n->release_persist();
     for (int& v : n->pdev_ok) v = -1;
     if (n->dev) { (void)hipFree(n->dev); n->dev = nullptr; }
@@ -496,6 +586,7 @@ FLAMED_API int flamed_dur_load(flamed_dur_t h, const float* const* w, int nw, hi
   size_t total = o_vec + a256(4 * vec_floats + 64 * 4);
   if (n->dev) { FL_HIP(hipFree(n->dev)); n->dev = nullptr; }
   n->graph.release();
+  n->graph_x.release();
   FL_HIP(hipMalloc(&n->dev, total));
   if (!n->split_mem) {  // slab: up to kSplitTarget workgroups of 32 x 64 fp32 tiles; zeroed tile counters
     const size_t slab_floats = (size_t)DurNet::kSplitTarget * 32 * 64;
@@ -540,15 +631,11 @@ FLAMED_API size_t flamed_pva_workspace_size(flamed_dur_t h, int B, int L, int nf
   return n ? pva_ws_layout(n, B, L, nfe, nullptr, nullptr) : 0;
 }
 
-FLAMED_API int flamed_pva_flow(flamed_dur_t dur, flamed_dur_t sil, const float* enc, const uint8_t* mask, float* dur_t,
-                               float* sil_t, const float* ts, int nfe, int B, int L, void* ws, size_t ws_bytes,
-                               int use_graph, hipStream_t st) {
-  DurNet* nd = reinterpret_cast<DurNet*>(dur);
-  DurNet* ns = reinterpret_cast<DurNet*>(sil);
-  FL_REQUIRE(nd && ns && nd->dev && ns->dev, "flamed_pva_flow: handles not loaded");
-  FL_REQUIRE(nd->D == ns->D && nd->F == ns->F, "flamed_pva_flow: dur/sil nets differ in dims");
-  FL_REQUIRE(enc && mask && dur_t && sil_t && ts && ws && nfe > 0 && B > 0 && L > 0, "flamed_pva_flow: bad args");
-  FL_REQUIRE(nd->device == ns->device, "flamed_pva_flow: dur/sil handles live on different devices");
+// The flow behind flamed_pva_flow (hlens null: dense, padding from `mask`) and flamed_pva_flow_exact (hlens: B host
+// lengths, already checked; `mask` null).  The arguments are checked by the two entry points.
+static int pva_flow_impl(DurNet* nd, DurNet* ns, const float* enc, const uint8_t* mask, const int* hlens, float* dur_t,
+                         float* sil_t, const float* ts, int nfe, int B, int L, void* ws, size_t ws_bytes, int use_graph,
+                         hipStream_t st) {
   std::unique_lock<std::mutex> lk_d(nd->mu, std::defer_lock), lk_s(ns->mu, std::defer_lock);
   if (nd == ns) lk_d.lock();
   else std::lock(lk_d, lk_s);
@@ -568,17 +655,24 @@ FLAMED_API int flamed_pva_flow(flamed_dur_t dur, flamed_dur_t sil, const float* 
   const float dt = (float)(1.0 / (double)nfe);
   const NetBufs bd{w.R1, w.S1, w.R2}, bs{w.R1s, w.S1s, w.R2s};
   int rc;
+  const int* dl = nullptr;
+  if (hlens) {  // stream-ordered ahead of the kernels / the replay below
+    bool moved = false;
+    if ((rc = nd->xlens.put(hlens, B, st, &moved))) return rc;
+    if (moved) retire_graph(nd->graph_x.exec), nd->graph_x.key.clear();
+    dl = nd->xlens.d;
+  }
   if ((rc = net_prepare(nd, enc, M, ts, nfe, w.Fd, w.TH, w.TEMBd, w.Pd, st))) return rc;
   if ((rc = net_prepare(ns, enc, M, ts, nfe, w.Fd, w.TH, w.TEMBs, w.Ps, st))) return rc;
   if ((use_graph & 1) && !(use_graph & 2) && pva_persist_eligible(nd, ns, M)) {
     bool done = false;
-    if ((rc = pva_persist_run(nd, ns, w, mask, dur_t, sil_t, nfe, B, L, dt, st, &done))) return rc;
+    if ((rc = pva_persist_run(nd, ns, w, mask, dur_t, sil_t, nfe, B, L, dt, st, &done, dl))) return rc;
     if (done) return kOk;
   }
   if (!(use_graph & 1)) {
     for (int i = 0; i < nfe; ++i) {  // dur then sil on every step (pva.py:104-109)
-      if ((rc = net_step(nd, w.Pd, w.TEMBd + (size_t)i * D, dur_t, mask, B, L, dt, bd, st))) return rc;
-      if ((rc = net_step(ns, w.Ps, w.TEMBs + (size_t)i * D, sil_t, mask, B, L, dt, bs, st))) return rc;
+      if ((rc = net_step(nd, w.Pd, w.TEMBd + (size_t)i * D, dur_t, mask, B, L, dt, bd, st, nullptr, nullptr, true, dl))) return rc;
+      if ((rc = net_step(ns, w.Ps, w.TEMBs + (size_t)i * D, sil_t, mask, B, L, dt, bs, st, nullptr, nullptr, true, dl))) return rc;
     }
     return kOk;
   }
@@ -589,9 +683,9 @@ FLAMED_API int flamed_pva_flow(flamed_dur_t dur, flamed_dur_t sil, const float* 
   int G = 1;
   for (int g = 16; g > 1; --g)
     if (nfe % g == 0) { G = g; break; }
-  PvaGraph& gp = nd->graph;
+  PvaGraph& gp = dl ? nd->graph_x : nd->graph;  // (the exact graph holds no length: its kernels read xlens)
   if (!gp.ctr) FL_HIP(hipMalloc(&gp.ctr, 256));
-  std::vector<const void*> key = {nd, ns, enc, mask, dur_t, sil_t, ts, ws, (const void*)(intptr_t)nfe,
+  std::vector<const void*> key = {nd, ns, enc, dl ? (const void*)dl : (const void*)mask, dur_t, sil_t, ts, ws, (const void*)(intptr_t)nfe,
                                   (const void*)(intptr_t)B, (const void*)(intptr_t)L, nd->dev, ns->dev,
                                   (const void*)(intptr_t)tune_ep};  // knobs (pva_split) are baked into the graph
   if (!gp.exec || gp.key != key) {
@@ -607,9 +701,9 @@ FLAMED_API int flamed_pva_flow(flamed_dur_t dur, flamed_dur_t sil, const float* 
     if (fe != hipSuccess) r = kHip;
     // one handle for both nets: its split-K counters would be shared by the concurrent branches
     const bool split = nd != ns;
-    for (int i = 0; i < G && r == kOk; ++i) r = net_step(nd, w.Pd, w.TEMBd, dur_t, mask, B, L, dt, bd, gp.cap, gp.ctr, gp.ctr, split);
+    for (int i = 0; i < G && r == kOk; ++i) r = net_step(nd, w.Pd, w.TEMBd, dur_t, mask, B, L, dt, bd, gp.cap, gp.ctr, gp.ctr, split, dl);
     for (int i = 0; i < G && r == kOk; ++i)
-      r = net_step(ns, w.Ps, w.TEMBs, sil_t, mask, B, L, dt, bs, gp.cap2, gp.ctr + 1, gp.ctr + 1, split);
+      r = net_step(ns, w.Ps, w.TEMBs, sil_t, mask, B, L, dt, bs, gp.cap2, gp.ctr + 1, gp.ctr + 1, split, dl);
     if (r == kOk) {
       fe = hipEventRecord(gp.join, gp.cap2);
       if (fe == hipSuccess) fe = hipStreamWaitEvent(gp.cap, gp.join, 0);
@@ -628,6 +722,35 @@ FLAMED_API int flamed_pva_flow(flamed_dur_t dur, flamed_dur_t sil, const float* 
   for (int r = 0; r < nfe / G; ++r) FL_HIP(hipGraphLaunch(gp.exec, st));
   note_graph_use(gp.exec, st);
   return kOk;
+}
+
+FLAMED_API int flamed_pva_flow(flamed_dur_t dur, flamed_dur_t sil, const float* enc, const uint8_t* mask, float* dur_t,
+                               float* sil_t, const float* ts, int nfe, int B, int L, void* ws, size_t ws_bytes,
+                               int use_graph, hipStream_t st) {
+  DurNet* nd = reinterpret_cast<DurNet*>(dur);
+  DurNet* ns = reinterpret_cast<DurNet*>(sil);
+  FL_REQUIRE(nd && ns && nd->dev && ns->dev, "flamed_pva_flow: handles not loaded");
+  FL_REQUIRE(nd->D == ns->D && nd->F == ns->F, "flamed_pva_flow: dur/sil nets differ in dims");
+  FL_REQUIRE(enc && mask && dur_t && sil_t && ts && ws && nfe > 0 && B > 0 && L > 0, "flamed_pva_flow: bad args");
+  FL_REQUIRE(nd->device == ns->device, "flamed_pva_flow: dur/sil handles live on different devices");
+  return pva_flow_impl(nd, ns, enc, mask, nullptr, dur_t, sil_t, ts, nfe, B, L, ws, ws_bytes, use_graph, st);
+}
+
+FLAMED_API int flamed_pva_flow_exact(flamed_dur_t dur, flamed_dur_t sil, const float* enc, const int* lens, float* dur_t,
+                                     float* sil_t, const float* ts, int nfe, int B, int L, void* ws, size_t ws_bytes,
+                                     int use_graph, hipStream_t st) {
+  // every check of the arguments comes before any pointer is touched
+  DurNet* nd = reinterpret_cast<DurNet*>(dur);
+  DurNet* ns = reinterpret_cast<DurNet*>(sil);
+  FL_REQUIRE(nd && ns, "flamed_pva_flow_exact: null handle");
+  FL_REQUIRE(enc && lens && dur_t && sil_t && ts && ws, "flamed_pva_flow_exact: null encoder output, lengths, state, time grid or workspace");
+  FL_REQUIRE(nfe > 0 && B > 0 && L > 0, "flamed_pva_flow_exact: bad dims nfe=%d B=%d L=%d", nfe, B, L);
+  for (int u = 0; u < B; ++u)
+    FL_REQUIRE(lens[u] >= 1 && lens[u] <= L, "flamed_pva_flow_exact: utterance %d has length %d (1..L = %d)", u, lens[u], L);
+  FL_REQUIRE(nd->dev && ns->dev, "flamed_pva_flow_exact: handles not loaded");
+  FL_REQUIRE(nd->D == ns->D && nd->F == ns->F, "flamed_pva_flow_exact: dur/sil nets differ in dims");
+  FL_REQUIRE(nd->device == ns->device, "flamed_pva_flow_exact: dur/sil handles live on different devices");
+  return pva_flow_impl(nd, ns, enc, nullptr, lens, dur_t, sil_t, ts, nfe, B, L, ws, ws_bytes, use_graph, st);
 }
 
 FLAMED_API int flamed_pva_persist_ready(flamed_dur_t dur, flamed_dur_t sil, int B, int L, hipStream_t st) {
@@ -672,7 +795,18 @@ FLAMED_API int flamed_lr_lengths(const float* phone, const float* sil, const int
   int dv = -1;
   (void)device_of(cum, &dv);
   FL_ON_DEVICE(dv);
-  hipLaunchKernelGGL(lr_lengths_kernel, dim3(B), dim3(256), 0, st, phone, sil, src_lens, L, log_domain, cum, tgt_len);
+  hipLaunchKernelGGL(lr_lengths_kernel<false>, dim3(B), dim3(256), 0, st, phone, sil, src_lens, L, log_domain, cum, tgt_len);
+  FL_LAUNCH_CHECK();
+  return kOk;
+}
+
+FLAMED_API int flamed_lr_lengths_exact(const float* phone, const float* sil, const int64_t* src_lens, int B, int L,
+                                       int log_domain, int64_t* cum, int64_t* tgt_len, hipStream_t st) {
+  FL_REQUIRE(phone && sil && src_lens && cum && tgt_len && B > 0 && L > 0, "flamed_lr_lengths_exact: bad args");
+  int dv = -1;
+  (void)device_of(cum, &dv);
+  FL_ON_DEVICE(dv);
+  hipLaunchKernelGGL(lr_lengths_kernel<true>, dim3(B), dim3(256), 0, st, phone, sil, src_lens, L, log_domain, cum, tgt_len);
   FL_LAUNCH_CHECK();
   return kOk;
 }

@@ -22,6 +22,7 @@
 //   LN + mask  R -> X (the last block of a decoder also writes its target rows into prior_embs)
 #include "flamed_hip.h"
 #include "gemm.hpp"
+#include "lens.hpp"
 #include "xfmr.hpp"
 
 #include <cmath>
@@ -92,6 +93,60 @@ __global__ void dec_input_kernel(const float* __restrict__ prev, int prev_bstrid
   if (c == 0) dmask[row] = j < P ? 0 : tmask[(size_t)b * T + (j - P)];
 }
 
+// Per-utterance prompt lengths (flamed_prior_decode_lens): utterance b has plens[b] <= P prompt codes, the first
+// plens[b] of its P slots.  Its sequence is left-compacted -- rows [0, P_b) the prompt, [P_b, P_b + T) the target
+// rows (target row t at position P_b + t), the last P - P_b rows padding -- which is the sequence it has alone plus
+// trailing padding: the key mask stays a prefix mask, so the attention kernels see nothing new.  Padding rows are
+// zero and masked; they are never a key, and the first masked LayerNorm zeroes them again.
+__global__ void dec_input_lens_kernel(const float* __restrict__ prev, int prev_bstride, const int64_t* __restrict__ prompts,
+                                      const int* __restrict__ plens, const float* __restrict__ cemb,
+                                      const float* __restrict__ pemb, const float* __restrict__ temb,
+                                      const float* __restrict__ qemb, const float* __restrict__ pos,
+                                      const uint8_t* __restrict__ tmask, int B, int P, int T, int D, int nq, int q,
+                                      float* __restrict__ X, uint8_t* __restrict__ dmask) {
+  const int n = P + T, D4 = D >> 2;
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * n * D4) return;
+  int row = i / D4, c = (i - row * D4) * 4;
+  int b = row / n, j = row - b * n;
+  int Pb = plens[b];
+  Pb = Pb < 0 ? 0 : (Pb < P ? Pb : P);
+  if (j >= Pb + T) {  // behind the utterance's own sequence
+    *reinterpret_cast<float4*>(X + (size_t)row * D + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c == 0) dmask[row] = 1;
+    return;
+  }
+  const float* src;
+  const float* seg;
+  if (j < Pb) {
+    src = cemb + (size_t)prompts[((size_t)b * nq + q) * P + j] * D;
+    seg = pemb;
+  } else {
+    src = prev + ((size_t)b * prev_bstride + (j - Pb)) * D;
+    seg = temb;
+  }
+  float4 s = ld4(src + c), g = ld4(seg + c), qe = ld4(qemb + c), p = ld4(pos + (size_t)j * D + c);
+  float4 o = make_float4(((s.x + g.x) + qe.x) + p.x, ((s.y + g.y) + qe.y) + p.y, ((s.z + g.z) + qe.z) + p.z,
+                         ((s.w + g.w) + qe.w) + p.w);
+  *reinterpret_cast<float4*>(X + (size_t)row * D + c) = o;
+  if (c == 0) dmask[row] = j < Pb ? 0 : tmask[(size_t)b * T + (j - Pb)];
+}
+
+// The decoder's target slice with per-utterance prompt lengths: embs[b][q][t] = X[b][plens[b] + t] (the dense
+// call's last LayerNorm writes rows j >= P itself; here the slice starts at the utterance's own prompt end).
+__global__ void dec_target_lens_kernel(const float* __restrict__ X, const int* __restrict__ plens, int B, int P, int T,
+                                       int D, int nq, int q, float* __restrict__ embs) {
+  const int D4 = D >> 2;
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * T * D4) return;
+  int row = i / D4, c = (i - row * D4) * 4;
+  int b = row / T, t = row - b * T;
+  int Pb = plens[b];
+  Pb = Pb < 0 ? 0 : (Pb < P ? Pb : P);
+  *reinterpret_cast<float4*>(embs + (((size_t)b * nq + q) * T + t) * D + c) =
+      ld4(X + ((size_t)b * (P + T) + Pb + t) * D + c);
+}
+
 // bridge(x) + position_enc[l] of the shared decoder (prior_generator.py:167 + Models.py:156-158)
 struct EpiBiasPos {
   const float* __restrict__ bias;
@@ -157,6 +212,8 @@ struct Prior {
   const float *prompt_emb = nullptr, *target_emb = nullptr, *q_emb = nullptr, *head_w = nullptr, *head_b = nullptr;
   int head_n = 0;  // padded head rows (multiple of 64)
   CapGraph genc, gdec;
+  CapGraph gdec_l;  // decode with prompt lengths: a graph of its own (it holds no length: the kernels read plens)
+  DevLens plens;
   int dec_dt = FLAMED_F32;  // decoder-side GEMM operands (flamed_prior_set_dtype)
   char* dev16 = nullptr;    // bf16 copies of the decoder-side GEMM weights (made on first bf16 decode)
   const bf16 *bridge_w16 = nullptr, *head_w16 = nullptr;
@@ -271,7 +328,8 @@ template <> const bf16* head_of<bf16>(const Prior* p) { return p->head_w16; }
 
 template <typename DT>
 static int run_decode(Prior* p, const float* x, const uint8_t* tmask, const int64_t* prompts, int B, int T, int P,
-                      const float* pos, float* embs, float* logits, const PriorWs& w, hipStream_t st) {
+                      const float* pos, float* embs, float* logits, const PriorWs& w, hipStream_t st,
+                      const int* plens = nullptr) {
   const int De = p->enc.D, D = p->shared.D, nq = p->nq;
   int rc;
   // bridge + shared decoder (prior_generator.py:165-168)
@@ -284,6 +342,17 @@ static int run_decode(Prior* p, const float* x, const uint8_t* tmask, const int6
   for (int q = 0; q < nq; ++q) {
     const float* prev = q == 0 ? w.Xs : embs + (size_t)(q - 1) * T * D;
     const int pbs = q == 0 ? T : nq * T;
+    if (plens) {  // per-utterance prompt lengths: left-compacted sequences, the target slice gathered behind the stack
+      hipLaunchKernelGGL(dec_input_lens_kernel, dim3((G + 255) / 256), dim3(256), 0, st, prev, pbs, prompts, plens,
+                         p->code_emb, p->prompt_emb, p->target_emb, p->q_emb + (size_t)q * D, pos ? pos : p->dec[q].pos,
+                         tmask, B, P, T, D, nq, q, w.X, w.dmask);
+      FL_LAUNCH_CHECK();
+      if ((rc = fft_forward<DT>(p->dec[q], w.X, w.dmask, B, n, w, st))) return rc;
+      const int GT = B * T * (D / 4);
+      hipLaunchKernelGGL(dec_target_lens_kernel, dim3((GT + 255) / 256), dim3(256), 0, st, w.X, plens, B, P, T, D, nq, q, embs);
+      FL_LAUNCH_CHECK();
+      continue;
+    }
     hipLaunchKernelGGL(dec_input_kernel, dim3((G + 255) / 256), dim3(256), 0, st, prev, pbs, prompts, p->code_emb,
                        p->prompt_emb, p->target_emb, p->q_emb + (size_t)q * D, pos ? pos : p->dec[q].pos, tmask, B, P, T,
                        D, nq, q, w.X, w.dmask);
@@ -384,6 +453,8 @@ FLAMED_API int flamed_prior_destroy(flamed_prior_t h) {
     DeviceGuard dg(p->device);
     p->genc.release();
     p->gdec.release();
+    p->gdec_l.release();
+    p->plens.release();
     if (p->dev) (void)hipFree(p->dev);
     if (p->dev16) (void)hipFree(p->dev16);
     if (p->split_mem) (void)hipFree(p->split_mem);
@@ -410,6 +481,8 @@ FLAMED_API int flamed_prior_load(flamed_prior_t h, const float* const* w, int nw
     DeviceGuard og(p->device);
     p->genc.release();
     p->gdec.release();
+    p->gdec_l.release();
+    p->plens.release();
     if (p->dev) { (void)hipFree(p->dev); p->dev = nullptr; }
     if (p->dev16) { (void)hipFree(p->dev16); p->dev16 = nullptr; }
   }
@@ -417,6 +490,7 @@ FLAMED_API int flamed_prior_load(flamed_prior_t h, const float* const* w, int nw
   FL_ON_DEVICE(wdev);
   p->genc.release();
   p->gdec.release();
+  p->gdec_l.release();
   if (p->dev) { FL_HIP(hipFree(p->dev)); p->dev = nullptr; }
   if (p->dev16) { FL_HIP(hipFree(p->dev16)); p->dev16 = nullptr; }  // stale copies: remade on the next bf16 decode
 
@@ -515,12 +589,28 @@ FLAMED_API int flamed_prior_encode(flamed_prior_t h, const int64_t* texts, const
 FLAMED_API int flamed_prior_decode(flamed_prior_t h, const float* x, const uint8_t* tgt_mask, const int64_t* prompts, int B,
                                    int T, int P, const float* pos, float* embs, float* logits, void* ws, size_t ws_bytes,
                                    int use_graph, hipStream_t st) {
+  return flamed_prior_decode_lens(h, x, tgt_mask, prompts, B, T, P, nullptr, pos, embs, logits, ws, ws_bytes, use_graph, st);
+}
+
+FLAMED_API int flamed_prior_decode_lens(flamed_prior_t h, const float* x, const uint8_t* tgt_mask, const int64_t* prompts,
+                                        int B, int T, int P, const int* prompt_lens, const float* pos, float* embs,
+                                        float* logits, void* ws, size_t ws_bytes, int use_graph, hipStream_t st) {
+  // every check of the arguments comes before any pointer is touched; prompt_lens null, or every length = P: the dense
+  // call itself
   Prior* p = reinterpret_cast<Prior*>(h);
   FL_REQUIRE(p && p->dev, "flamed_prior_decode: handle not loaded");
   FL_REQUIRE(x && tgt_mask && embs && logits && ws && B > 0 && T > 0 && P >= 0 && (P == 0 || prompts),
              "flamed_prior_decode: bad args");
   FL_REQUIRE(pos || P + T <= p->shared.maxseq, "flamed_prior_decode: P+T=%d exceeds the position table (%d): pass a table",
              P + T, p->shared.maxseq);
+  const int* hl = nullptr;
+  if (prompt_lens) {
+    for (int u = 0; u < B; ++u) {
+      FL_REQUIRE(prompt_lens[u] >= 0 && prompt_lens[u] <= P, "flamed_prior_decode_lens: utterance %d has prompt length %d (0..P = %d)",
+                 u, prompt_lens[u], P);
+      if (prompt_lens[u] != P) hl = prompt_lens;
+    }
+  }
   std::lock_guard<std::mutex> lk(p->mu);
   FL_ON_DEVICE(p->device);
   FL_REQUIRE_ON(embs, p->device, "flamed_prior_decode");
@@ -540,10 +630,18 @@ FLAMED_API int flamed_prior_decode(flamed_prior_t h, const float* x, const uint8
   std::vector<const void*> key = {x, tgt_mask, prompts, pos, embs, logits, ws, (const void*)(intptr_t)B,
                                   (const void*)(intptr_t)T, (const void*)(intptr_t)P, p->dev,
                                   (const void*)(intptr_t)p->dec_dt, p->dev16};
-  return with_graph(p->gdec, key, use_graph != 0, st, [&](hipStream_t s) {
-    if (!b16) return run_decode<float>(p, x, tgt_mask, prompts, B, T, P, pos, embs, logits, w, s);
+  const int* dl = nullptr;
+  if (hl) {  // stream-ordered ahead of the kernels / the replay below; the key is the dense key plus the array
+    bool moved = false;
+    const int rc = p->plens.put(hl, B, st, &moved);
+    if (rc) return rc;
+    dl = p->plens.d;
+    key.push_back(dl);
+  }
+  return with_graph(dl ? p->gdec_l : p->gdec, key, use_graph != 0, st, [&](hipStream_t s) {
+    if (!b16) return run_decode<float>(p, x, tgt_mask, prompts, B, T, P, pos, embs, logits, w, s, dl);
     SplitScope sc(tn().prior_split ? &p->split : nullptr);
-    return run_decode<bf16>(p, x, tgt_mask, prompts, B, T, P, pos, embs, logits, w, s);
+    return run_decode<bf16>(p, x, tgt_mask, prompts, B, T, P, pos, embs, logits, w, s, dl);
   });
 }
 

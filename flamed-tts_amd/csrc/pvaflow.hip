@@ -207,7 +207,11 @@ struct AConv2S {
 
 // ST (Params::stage): row groups of >= 2 tiles take conv_st (the per-lane gather loops of those groups are not
 // compiled in, so the staged kernel does not carry their registers)
-template <int D, int F, bool ST>
+// EX (Params::lens): exact lengths.  Utterance u of the padded batch owns rows [u L, u L + lens[u]); both convs'
+// windows are cut at that end instead of at L, rows behind it are dead (no tap of theirs is read, no valid row
+// reads them) and their state is 0 from the first step to the write-back, so every utterance gets the flow it
+// would get alone.  The mask is not read.  The dense instantiation (EX = false) is the kernel as it always was.
+template <int D, int F, bool ST, bool EX>
 __global__ __launch_bounds__(kThreads, 1) void pva_persist_kernel(Params P) {
   using LY = Lds<D, F>;
   constexpr int K1 = LY::K1, K2 = LY::K2, CS = LY::CS, NB1 = K1 / 16, NB2 = K2 / 16;
@@ -227,6 +231,7 @@ __global__ __launch_bounds__(kThreads, 1) void pva_persist_kernel(Params P) {
   float* sa = reinterpret_cast<float*>(smem + LY::SA);  // staged A window (one-tile groups)
   float* uv = reinterpret_cast<float*>(smem + LY::UV);  // staged conv1: U[tap][c] = W1_tap,c . w0, V[tap][c] = W1_tap,c . temb_s
   int* flag = reinterpret_cast<int*>(smem + LY::FLAG);
+  int* ul = reinterpret_cast<int*>(smem + LY::UL);  // EX: length of the utterance of window row r0 - 1 + i (0 outside the batch)
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -248,7 +253,10 @@ __global__ __launch_bounds__(kThreads, 1) void pva_persist_kernel(Params P) {
   // this launch used, for the next launch.
   auto leave = [&](bool ok) {
     if (!ok && cs == 0)
-      for (int i = tid; i < nr; i += kThreads) N.xt[r0 + i] = __builtin_nanf("");
+      for (int i = tid; i < nr; i += kThreads) {
+        if constexpr (EX) N.xt[r0 + i] = (r0 + i) % L < ul[i + 1] ? __builtin_nanf("") : 0.f;  // valid rows only
+        else N.xt[r0 + i] = __builtin_nanf("");
+      }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0)
@@ -267,6 +275,26 @@ __global__ __launch_bounds__(kThreads, 1) void pva_persist_kernel(Params P) {
       }
     }
   };
+
+  // length of row m's utterance (EX: from the window table; m - xa < XR for every tile row of a group) and whether
+  // the row itself lies inside it
+  auto ulen = [&](int m) -> int {
+    if constexpr (EX) return ul[m - xa];
+    else return L;
+  };
+  auto inside = [&](int m) -> bool {
+    if constexpr (EX) return m < M && m % L < ul[m - xa];
+    else return true;
+  };
+  if constexpr (EX) {
+    for (int i = tid; i < LY::XR; i += kThreads) {
+      const int r = xa + i;
+      int n = 0;
+      if (r >= 0 && r < M) n = min(max(P.lens[r / L], 0), L);
+      ul[i] = n;
+    }
+    __syncthreads();
+  }
 
   // ---- resident state: this workgroup's weight columns of both convs, shared vectors, x_t window
   for (int i = tid; i < kCols * K1 / 4; i += kThreads) {
@@ -293,7 +321,8 @@ __global__ __launch_bounds__(kThreads, 1) void pva_persist_kernel(Params P) {
   }
   for (int i = tid; i < nw; i += kThreads) {
     const int r = xa + i;
-    xs[i] = (r >= 0 && r < M) ? N.xt[r] : 0.f;
+    if constexpr (EX) xs[i] = (r >= 0 && r < M && r % L < ul[i]) ? N.xt[r] : 0.f;  // padding is never read
+    else xs[i] = (r >= 0 && r < M) ? N.xt[r] : 0.f;
   }
   const float bias1 = N.c1b[col0 + c], bias2 = N.c2b[col0 + c];
   const float gl = N.g2[col0 + c] * N.lw[col0 + c];
@@ -379,7 +408,7 @@ __global__ __launch_bounds__(kThreads, 1) void pva_persist_kernel(Params P) {
       f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
       const int t = tw + 4 * pass;
       const int m = r0 + 16 * t + c;
-      const bool live = t < nt && m < r0 + nr;
+      const bool live = t < nt && m < r0 + nr && inside(m);
       const int lm = live ? m % L : 0;
       auto stage = [&](int k) __attribute__((always_inline)) {
         float* buf = sa + (k & 1) * (PROWS + 1) * CBS;
@@ -424,7 +453,7 @@ __global__ __launch_bounds__(kThreads, 1) void pva_persist_kernel(Params P) {
 #pragma unroll
           for (int v = 0; v < UG; ++v) {
             const int u = u0 + v, tap = u / (NU / 3), l = lm + tap - 1;
-            const unsigned vm = (live && l >= 0 && l < L) ? ~0u : 0u;
+            const unsigned vm = (live && l >= 0 && l < ulen(m)) ? ~0u : 0u;
             const float4 a = make_float4(__uint_as_float(__float_as_uint(ar[v].x) & vm), __uint_as_float(__float_as_uint(ar[v].y) & vm),
                                          __uint_as_float(__float_as_uint(ar[v].z) & vm), __uint_as_float(__float_as_uint(ar[v].w) & vm));
             const float4 b = br[v];
@@ -564,7 +593,8 @@ __global__ __launch_bounds__(kThreads, 1) void pva_persist_kernel(Params P) {
             const int l = lm + tap - 1;
             const float x = xs[row + tap];  // window index of frame m + tap - 1 (xa = r0 - 1)
             const float term = fmaf(x, uv[tap * kCols + c], uv[3 * kCols + tap * kCols + c]);
-            sum += (m < r0 + nr && l >= 0 && l < L) ? term : 0.f;
+            if constexpr (EX) sum += (m < r0 + nr && l >= 0 && l < ul[row + 1] && lm < ul[row + 1]) ? term : 0.f;
+            else sum += (m < r0 + nr && l >= 0 && l < L) ? term : 0.f;
           }
           acc[i] += sum;
         }
@@ -575,12 +605,14 @@ __global__ __launch_bounds__(kThreads, 1) void pva_persist_kernel(Params P) {
          [&](int t) {
            const int m = r0 + 16 * t + c;
            const bool live = m < r0 + nr;
-           return AConv1<D>{N.P, vw0, vte, xs, m, live ? m % L : 0, L, xa, q, live};
+           const int lm = live ? m % L : 0, Lr = ulen(m);
+           return AConv1<D>{N.P, vw0, vte, xs, m, lm, Lr, xa, q, live && inside(m)};
          },
          [&](int t) {
            const int m = r0 + 16 * t + c;
            const bool live = m < r0 + nr;
-           return AConv1S<D, F>{sa, vw0, vte, xs, m, live ? m % L : 0, L, xa, q, live};
+           const int lm = live ? m % L : 0, Lr = ulen(m);
+           return AConv1S<D, F>{sa, vw0, vte, xs, m, lm, Lr, xa, q, live && inside(m)};
          },
          epi1);
     }
@@ -665,12 +697,14 @@ __global__ __launch_bounds__(kThreads, 1) void pva_persist_kernel(Params P) {
          [&](int t) {
            const int m = r0 + 16 * t + c;
            const bool live = m < r0 + nr;
-           return AConv2<F>{rR1, st, vg1, vb1, m, live ? m % L : 0, L, xa, q, live};
+           const int lm = live ? m % L : 0, Lr = ulen(m);
+           return AConv2<F>{rR1, st, vg1, vb1, m, lm, Lr, xa, q, live && inside(m)};
          },
          [&](int t) {
            const int m = r0 + 16 * t + c;
            const bool live = m < r0 + nr;
-           return AConv2S<F>{sa, m, live ? m % L : 0, L, xa, q, live};
+           const int lm = live ? m % L : 0, Lr = ulen(m);
+           return AConv2S<F>{sa, m, lm, Lr, xa, q, live && inside(m)};
          },
          epi2);
     }
@@ -701,8 +735,13 @@ __global__ __launch_bounds__(kThreads, 1) void pva_persist_kernel(Params P) {
         float dot = 0.f;
 #pragma unroll
         for (int k = 0; k < CS; ++k) dot += pp[k].z + (pp[k].x - mean) * gs[k];
-        const float vel = P.mask[r] ? 0.f : (rstd * dot + gs[CS]) + lb;
-        xs[tid] = __fadd_rn(xs[tid], __fmul_rn(P.dt, vel));
+        if constexpr (EX) {  // rows behind the utterance's end stay 0 (their partials are never relied on)
+          const float vel = (rstd * dot + gs[CS]) + lb;
+          xs[tid] = r % L < ul[tid] ? __fadd_rn(xs[tid], __fmul_rn(P.dt, vel)) : 0.f;
+        } else {
+          const float vel = P.mask[r] ? 0.f : (rstd * dot + gs[CS]) + lb;
+          xs[tid] = __fadd_rn(xs[tid], __fmul_rn(P.dt, vel));
+        }
       }
     }
     __syncthreads();
@@ -718,11 +757,13 @@ size_t pva_persist_lds() { return (size_t)Lds<192, 384>::BYTES; }
 bool pva_persist_device_ok(int device, int grid) {
   int cus = 0, nb = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < grid) return false;
-  for (const void* k : {reinterpret_cast<const void*>(pva_persist_kernel<192, 384, true>),
-                        reinterpret_cast<const void*>(pva_persist_kernel<192, 384, false>)}) {
-    if (set_max_lds(k) != hipSuccess) return false;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kThreads, Lds<192, 384>::BYTES) != hipSuccess || nb < 1)
-      return false;
+  struct K { const void* fn; size_t lds; };  // every instantiation with the LDS it is launched with
+  for (const K& k : {K{reinterpret_cast<const void*>(pva_persist_kernel<192, 384, true, false>), Lds<192, 384>::BYTES},
+                     K{reinterpret_cast<const void*>(pva_persist_kernel<192, 384, false, false>), Lds<192, 384>::BYTES},
+                     K{reinterpret_cast<const void*>(pva_persist_kernel<192, 384, true, true>), Lds<192, 384>::BYTES_EX},
+                     K{reinterpret_cast<const void*>(pva_persist_kernel<192, 384, false, true>), Lds<192, 384>::BYTES_EX}}) {
+    if (set_max_lds(k.fn) != hipSuccess) return false;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k.fn, kThreads, k.lds) != hipSuccess || nb < 1) return false;
   }
   return true;
 }
@@ -737,11 +778,15 @@ int pva_persist_launch(const Params& Pin, hipStream_t st) {
   // cooperative: the runtime checks the grid against the occupancy and refuses it up front; a captured
   // cooperative launch replays cooperatively
   void* args[] = {&P};
-  const void* kern = P.stage ? reinterpret_cast<const void*>(pva_persist_kernel<192, 384, true>)
-                             : reinterpret_cast<const void*>(pva_persist_kernel<192, 384, false>);
+  const bool ex = P.lens != nullptr;  // exact lengths: the EX instantiations, with the window table behind the dense carve
+  const void* kern = ex ? (P.stage ? reinterpret_cast<const void*>(pva_persist_kernel<192, 384, true, true>)
+                                   : reinterpret_cast<const void*>(pva_persist_kernel<192, 384, false, true>))
+                        : (P.stage ? reinterpret_cast<const void*>(pva_persist_kernel<192, 384, true, false>)
+                                   : reinterpret_cast<const void*>(pva_persist_kernel<192, 384, false, false>));
+  const size_t lds = ex ? Lds<192, 384>::BYTES_EX : Lds<192, 384>::BYTES;
   // tune coop 0: plain launch (profiling, README "Known issues"); residency checked by pva_persist_eligible
-  const hipError_t e = tn().coop ? hipLaunchCooperativeKernel(kern, dim3(P.grid), dim3(kThreads), args, Lds<192, 384>::BYTES, st)
-                                 : hipLaunchKernel(kern, dim3(P.grid), dim3(kThreads), args, Lds<192, 384>::BYTES, st);
+  const hipError_t e = tn().coop ? hipLaunchCooperativeKernel(kern, dim3(P.grid), dim3(kThreads), args, lds, st)
+                                 : hipLaunchKernel(kern, dim3(P.grid), dim3(kThreads), args, lds, st);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     set_error("persistent PVA flow: hipLaunchCooperativeKernel -> %s", hipGetErrorString(e));

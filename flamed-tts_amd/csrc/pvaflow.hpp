@@ -64,6 +64,7 @@ struct Params {
   int stage = 1;         // row groups of >= 2 tiles: conv A windows staged through LDS in 32-channel chunks (tune pva_stage)
   unsigned long long* pst = nullptr;  // FL_STAMPS builds: per-workgroup timeline of step pst_step
   int pst_step = -1;
+  const int* lens = nullptr;  // exact lengths: B device ints, utterance u owns rows [u L, u L + lens[u]); null = dense
 };
 constexpr int kStampSlots = 16;
 
@@ -79,6 +80,9 @@ struct Lds {
   // 64-channel chunk of a 4-tile pass window (66 rows, padded by 16 B), in the same bytes
   static constexpr int FC = 64, CBS = FC + 4, WMAX = kMaxRowsWG + 2, PROWS = 4 * 16 + 2, SA1 = 18 * SAS * 4,
                        SA2 = 2 * (PROWS + 1) * CBS * 4, BYTES = SA + (SA1 > SA2 ? SA1 : SA2);  // (+ a spare row)
+  // exact lengths only: the window rows' utterance lengths, behind the dense carve (the dense launch's LDS is BYTES)
+  static constexpr int UL = BYTES, BYTES_EX = BYTES + XR * 4;
+  static_assert(UL % 4 == 0 && BYTES_EX <= 160 * 1024, "pva persist LDS (exact lengths)");
   static_assert(K1 % 64 == 0 && K2 % 64 == 0 && D % 16 == 0 && F % kCols == 0, "pva persist dims");
   static_assert(RED % 16 == 0 && BYTES <= 160 * 1024, "pva persist LDS");
 };

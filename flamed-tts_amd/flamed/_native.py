@@ -62,10 +62,12 @@ SIGNATURES = {
     "flamed_dur_load": (c_int, [P, ctypes.POINTER(P), c_int, P]),
     "flamed_pva_workspace_size": (c_size_t, [P, c_int, c_int, c_int]),
     "flamed_pva_flow": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, P, c_size_t, c_int, P]),
+    "flamed_pva_flow_exact": (c_int, [P, P, P, ctypes.POINTER(c_int), P, P, P, c_int, c_int, c_int, P, c_size_t, c_int, P]),
     "flamed_pva_persist_info": (c_int, [P, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_float)]),
     "flamed_pva_persist_ready": (c_int, [P, P, c_int, c_int, P]),
     "flamed_pva_persist_status": (c_int, [P, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "flamed_lr_lengths": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P]),
+    "flamed_lr_lengths_exact": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P]),
     "flamed_lr_expand": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P]),
     "flamed_fac_create": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int), c_int, ctypes.POINTER(P)]),
     "flamed_fac_destroy": (c_int, [P]),
@@ -94,6 +96,8 @@ SIGNATURES = {
     "flamed_prior_workspace_size": (c_size_t, [P, c_int, c_int, c_int, c_int]),
     "flamed_prior_encode": (c_int, [P, P, P, c_int, c_int, P, P, P, c_size_t, c_int, P]),
     "flamed_prior_decode": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P, P, P, c_size_t, c_int, P]),
+    "flamed_prior_decode_lens": (c_int, [P, P, P, P, c_int, c_int, c_int, ctypes.POINTER(c_int), P, P, P, P, c_size_t, c_int,
+                                         P]),
     "flamed_prior_set_dtype": (c_int, [P, c_int]),
 }
 

@@ -72,11 +72,11 @@ class Flamed(nn.Module):
                timbre: torch.Tensor = None, sr: int = 16000, codec_cfg=None, codec_encoder=None, codec_decoder=None,
                temp_durgen: float = 0.3, temp_denoiser: float = 0.3, nsteps_durgen: int = 64,
                nsteps_denoiser: int = 64, lexicon_path: str = None, cleaners=("english_cleaners",),
-               solver_denoiser: str = "euler", exact_lengths: bool = False):
+               solver_denoiser: str = "euler", exact_lengths: bool = False, exact_prior: bool = False):
         """reference :89-166 (same argument validation and ValueErrors).  solver_denoiser: the denoiser's ODE
         solver ("euler", the reference's; "midpoint" / "heun": second order, nsteps_denoiser then counts velocity
         evaluations and must be even -- ProbGenerator.sample).  exact_lengths: as in sample_batch (one utterance has
-        no padding, so it changes nothing here)."""
+        no padding, so it changes nothing here); exact_prior likewise."""
         if codec_decoder is None or (codec_encoder is None and prompt_raw is not None):
             if codec_cfg is None:
                 raise ValueError("The codec_encoder or codec_decoder is set to None. To initialize the codec encoder or "
@@ -113,26 +113,42 @@ class Flamed(nn.Module):
                                 prompts=prompts, timbres=timbre, codec_decoder=codec_decoder, temp_durgen=temp_durgen,
                                 temp_denoiser=temp_denoiser, nsteps_durgen=nsteps_durgen,
                                 nsteps_denoiser=nsteps_denoiser, solver_denoiser=solver_denoiser,
-                                exact_lengths=exact_lengths)
+                                exact_lengths=exact_lengths, exact_prior=exact_prior)
         wav = out["wav"][0][0].detach().cpu().numpy()
         return {"wav": wav, "time": time.time() - start}
 
     @torch.inference_mode()
     def sample_batch(self, phonemes, src_lens, prompts, timbres, codec_decoder=None, temp_durgen: float = 0.3,
                      temp_denoiser: float = 0.3, nsteps_durgen: int = 64, nsteps_denoiser: int = 64,
-                     solver_denoiser: str = "euler", exact_lengths: bool = False):
+                     solver_denoiser: str = "euler", exact_lengths: bool = False, exact_prior: bool = False,
+                     prompt_lens=None):
         """reference :168-217; solver_denoiser as in sample.  exact_lengths (opt-in): every utterance of the padded
         batch gets the latents it would get alone -- its condition fold and its solve run over its own frames only
         and its padding frames are 0 (ProbGenerator.sample), and the FaCodec decode gets lens = (~tgt_mask).sum(-1), so
         wav[u, :, :wav_lens[u]] is the waveform utterance u would get alone and wav[u, :, wav_lens[u]:] is exactly 0
         (FACodecDecoder.inference(..., lens)).  outputs["wav_lens"] (samples, hop * len_u; with a codec_decoder and the
-        flag only) tells where each waveform ends; without the flag there is no such key and wav is as before."""
+        flag only) tells where each waveform ends; without the flag there is no such key and wav is as before.
+        exact_prior (opt-in, independent of exact_lengths): the stage in front -- duration flow, length regulator, prior
+        decoders -- gives every utterance what it would get alone (PriorGenerator.sample(exact_lengths=True)): its
+        durations come from its own phonemes, tgt_mask holds its own frame count, and it is decoded behind its own
+        prompt.  prompt_lens (B ints) tells how many codes of prompts[u] are real; None with the flag: the count of
+        prompts[u, 0] != vocab_size, the pad id of a padded batch of prompts (ValueError if the real codes are not a
+        prefix, or if an utterance's quantizers disagree).  Both flags together make wav[u, :, :wav_lens[u]]
+        independent of the batch."""
         start = time.time()
         dev = self.device
         phonemes, src_lens, prompts, timbres = phonemes.to(dev), src_lens.to(dev), prompts.to(dev), timbres.to(dev)
-        prior_emb_cond, prior_logits, tgt_mask = self.prior_generator.sample(
-            texts=phonemes, src_lens=src_lens, max_src_len=phonemes.size(-1), prompts=prompts,
-            prompts_len=prompts.size(-1), nfe=nsteps_durgen, temperature=temp_durgen)
+        if exact_prior or prompt_lens is not None:
+            if prompt_lens is None:
+                prompt_lens = self._prompt_lens_from_pad(prompts)
+            prior_emb_cond, prior_logits, tgt_mask = self.prior_generator.sample(
+                texts=phonemes, src_lens=src_lens, max_src_len=phonemes.size(-1), prompts=prompts,
+                prompts_len=prompts.size(-1), nfe=nsteps_durgen, temperature=temp_durgen,
+                exact_lengths=bool(exact_prior), prompt_lens=prompt_lens)
+        else:
+            prior_emb_cond, prior_logits, tgt_mask = self.prior_generator.sample(
+                texts=phonemes, src_lens=src_lens, max_src_len=phonemes.size(-1), prompts=prompts,
+                prompts_len=prompts.size(-1), nfe=nsteps_durgen, temperature=temp_durgen)
         latents = self.prob_generator.sample(cond=prior_emb_cond, spk=timbres, nfe=nsteps_denoiser,
                                              temperature=temp_denoiser, mask=~tgt_mask.unsqueeze(-1),
                                              solver=solver_denoiser, exact_lengths=exact_lengths)
@@ -150,6 +166,20 @@ class Flamed(nn.Module):
         elif codec_decoder is not None:
             outputs["wav"] = codec_decoder.inference(latents, timbres)
         return outputs
+
+    def _prompt_lens_from_pad(self, prompts):
+        """Per-utterance prompt lengths of a (B, n_q, P) batch of codes padded with the pad id vocab_size."""
+        pad = self.prior_generator.code_embedding.padding_idx
+        real = prompts != pad
+        lens = real.sum(-1)  # (B, n_q)
+        P = prompts.size(-1)
+        prefix = real == (torch.arange(P, device=prompts.device) < lens.unsqueeze(-1))
+        if not bool(prefix.all()):
+            raise ValueError("exact_prior: the pad id must only follow an utterance's prompt codes (the real codes "
+                             "are not a prefix); pass prompt_lens")
+        if not bool((lens == lens[:, :1]).all()):
+            raise ValueError("exact_prior: the quantizers of an utterance's prompt differ in length; pass prompt_lens")
+        return [int(n) for n in lens[:, 0].tolist()]
 
     def _preprocess_acoustic_prompt(self, acoustic_prompt, sr=16000):
         if isinstance(acoustic_prompt, str):

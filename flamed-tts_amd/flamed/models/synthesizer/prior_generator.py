@@ -114,17 +114,52 @@ class PriorGenerator(nn.Module):
         loss = sum(F.cross_entropy(logits[:, :, i, :], codes[:, i, :]) for i in range(codes.size(1))) / codes.size(1)
         return output, tgt_masks, pva_losses | {"prior_loss": loss}
 
-    def sample(self, texts, src_lens, max_src_len, prompts, prompts_len, nfe=4, temperature=1.0):
-        """reference :141-196 -> (prior embeddings (B,Q,T,D), logits (B,V+1,Q,T), tgt mask (B,T))."""
+    def _decode_each_alone(self, output, tgt_lens, tgt_masks, prompts, prompt_lens):
+        """The decode with per-utterance prompt lengths on torch ops: every utterance alone, over its own frames
+        and behind its own prompt, written into the padded outputs (0 behind every end)."""
+        B, T, _ = output.shape
+        nq, D, V1 = len(self.prior_decoder), self.head.in_features, self.head.out_features
+        embs = output.new_zeros((B, nq, T, D))
+        logits = output.new_zeros((B, V1, nq, T))
+        for u in range(B):
+            Tu, Pu = int(tgt_lens[u]), int(prompt_lens[u])
+            if Tu == 0:
+                continue
+            mask = torch.zeros((1, Tu), dtype=torch.bool, device=output.device)
+            e, lg, _ = self._decode(self.bridge(output[u:u + 1, :Tu]), tgt_lens[u:u + 1], mask, prompts[u:u + 1, :, :Pu], Pu)
+            embs[u, :, :Tu], logits[u, :, :, :Tu] = e[0], lg[0]
+        return embs, logits, tgt_masks
+
+    def sample(self, texts, src_lens, max_src_len, prompts, prompts_len, nfe=4, temperature=1.0, exact_lengths=False,
+               prompt_lens=None):
+        """reference :141-196 -> (prior embeddings (B,Q,T,D), logits (B,V+1,Q,T), tgt mask (B,T)).
+        exact_lengths (opt-in, no reference counterpart): every utterance of the padded batch gets the durations, the
+        frame count, the prior embeddings and the logits it would get alone, from its own slice of the same noise
+        draws (PVA.flow / LengthRegulator.LR with exact=True); everything behind an utterance's end is 0.
+        prompt_lens (B ints, 0 <= prompt_lens[u] <= prompts_len; None = prompts_len for all): utterance u's prompt is
+        prompts[u, :, :prompt_lens[u]]; the decoders then see its own prompt only and place target frame t at
+        position prompt_lens[u] + t."""
         src_masks = get_mask_from_lengths(src_lens, max_src_len)
         hip = self._use_hip(texts)
         output = ops.prior_encode(self.hip().oid, texts, src_masks) if hip else self.encoder(texts, src_masks)
-        output, tgt_lens = self.pva.sample(output, src_lens, src_masks, nfe=nfe, temperature=temperature)
+        if not exact_lengths and prompt_lens is None:
+            output, tgt_lens = self.pva.sample(output, src_lens, src_masks, nfe=nfe, temperature=temperature)
+            tgt_masks = get_mask_from_lengths(tgt_lens, output.size(1))
+            if hip:
+                embs, logits = ops.prior_decode(self.hip().oid, output, tgt_masks, prompts, int(prompts_len))
+                return embs, logits, tgt_masks
+            return self._decode(self.bridge(output), tgt_lens, tgt_masks, prompts, prompts_len)
+        P = int(prompts_len)
+        plens = [P] * texts.size(0) if prompt_lens is None else [int(n) for n in torch.as_tensor(prompt_lens).tolist()]
+        if len(plens) != texts.size(0) or any(n < 0 or n > P for n in plens):
+            raise ValueError(f"prompt_lens must hold one length in [0, {P}] per utterance (got {plens})")
+        output, tgt_lens = self.pva.sample(output, src_lens, src_masks, nfe=nfe, temperature=temperature,
+                                           exact=bool(exact_lengths))
         tgt_masks = get_mask_from_lengths(tgt_lens, output.size(1))
         if hip:
-            embs, logits = ops.prior_decode(self.hip().oid, output, tgt_masks, prompts, int(prompts_len))
+            embs, logits = ops.prior_decode_lens(self.hip().oid, output, tgt_masks, prompts, P, plens)
             return embs, logits, tgt_masks
-        return self._decode(self.bridge(output), tgt_lens, tgt_masks, prompts, prompts_len)
+        return self._decode_each_alone(output, tgt_lens, tgt_masks, prompts, plens)
 
 
 def _fft_layer_weights(layer) -> List[torch.Tensor]:
@@ -232,9 +267,10 @@ class PriorHIP:
                                         int(bool(self.pg.hip_graph)), nat.stream_ptr(dev)), "flamed_prior_encode")
         return bufs["out"].clone()
 
-    def decode(self, x: torch.Tensor, tgt_mask: torch.Tensor, prompts: torch.Tensor, P: int):
+    def decode(self, x: torch.Tensor, tgt_mask: torch.Tensor, prompts: torch.Tensor, P: int, prompt_lens=None):
         """x (B, T, enc hidden) regulated encoder output, tgt_mask (B, T) bool, prompts (B, n_q, P) codes ->
-        (prior embeddings (B, n_q, T, hidden), logits (B, vocab+1, n_q, T))."""
+        (prior embeddings (B, n_q, T, hidden), logits (B, vocab+1, n_q, T)).  prompt_lens (B ints in [0, P]):
+        utterance u is decoded behind prompts[u, :, :prompt_lens[u]] only, as if alone (flamed_prior_decode_lens)."""
         dev = x.device
         self._ensure(dev)
         B, T, De = x.shape
@@ -258,8 +294,18 @@ class PriorHIP:
         nat.check(L.flamed_prior_set_dtype(self.handle, nat.FLAMED_BF16 if pg.hip_dec_dtype == "bf16" else nat.FLAMED_F32),
                   "flamed_prior_set_dtype")
         ws = self.ws.get(L.flamed_prior_workspace_size(self.handle, B, 0, T, P), dev)
-        nat.check(L.flamed_prior_decode(self.handle, nat.ptr(bufs["x"]), nat.ptr(bufs["mask"]), nat.ptr(bufs["prompts"]),
-                                        B, T, P, nat.ptr(bufs["pos"]), nat.ptr(bufs["embs"]), nat.ptr(bufs["logits"]),
-                                        nat.ptr(ws), ws.numel(), int(bool(pg.hip_graph)), nat.stream_ptr(dev)),
-                  "flamed_prior_decode")
+        if prompt_lens is None:
+            nat.check(L.flamed_prior_decode(self.handle, nat.ptr(bufs["x"]), nat.ptr(bufs["mask"]), nat.ptr(bufs["prompts"]),
+                                            B, T, P, nat.ptr(bufs["pos"]), nat.ptr(bufs["embs"]), nat.ptr(bufs["logits"]),
+                                            nat.ptr(ws), ws.numel(), int(bool(pg.hip_graph)), nat.stream_ptr(dev)),
+                      "flamed_prior_decode")
+        else:
+            if len(prompt_lens) != B:
+                raise ValueError(f"prior decode: {len(prompt_lens)} prompt lengths for a batch of {B}")
+            arr = (ctypes.c_int * B)(*[int(n) for n in prompt_lens])
+            nat.check(L.flamed_prior_decode_lens(self.handle, nat.ptr(bufs["x"]), nat.ptr(bufs["mask"]),
+                                                 nat.ptr(bufs["prompts"]), B, T, P, arr, nat.ptr(bufs["pos"]),
+                                                 nat.ptr(bufs["embs"]), nat.ptr(bufs["logits"]), nat.ptr(ws), ws.numel(),
+                                                 int(bool(pg.hip_graph)), nat.stream_ptr(dev)),
+                      "flamed_prior_decode_lens")
         return bufs["embs"].clone(), bufs["logits"].clone()

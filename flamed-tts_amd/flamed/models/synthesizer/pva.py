@@ -126,9 +126,11 @@ def _lr_hip_ok(x: torch.Tensor) -> bool:
 class LengthRegulator(nn.Module):
     """Interleaved phone/silence length regulation (reference pva.py:119-170)."""
 
-    def LR(self, x, phone_duration, sil_duration, src_lens, max_len, log_domain=False):
+    def LR(self, x, phone_duration, sil_duration, src_lens, max_len, log_domain=False, exact=False):
+        """exact (opt-in, no reference counterpart): a padded phoneme repeats 0 frames instead of the reference's 1
+        (its clamp(min=1) runs after the where), so tgt_len is the length every utterance has alone."""
         if _lr_hip_ok(x):
-            return hip_length_regulate(x, phone_duration, sil_duration, src_lens, max_len, log_domain)
+            return hip_length_regulate(x, phone_duration, sil_duration, src_lens, max_len, log_domain, exact)
         if log_domain:
             phone_duration = torch.clamp(torch.round(torch.exp(phone_duration) - 1), min=0)
             sil_duration = torch.clamp(torch.round(torch.exp(sil_duration) - 1), min=0)
@@ -137,6 +139,8 @@ class LengthRegulator(nn.Module):
         zero = torch.zeros_like(phone_duration, dtype=torch.float32)
         pr = torch.clamp(torch.where(valid, phone_duration.float(), zero).round().long(), min=1)
         sr = torch.clamp(torch.where(valid, sil_duration.float(), zero).round().long(), min=0)
+        if exact:
+            pr = torch.where(valid, pr, torch.zeros_like(pr))
         seg = torch.stack((x, x[:, :1, :].expand(-1, L, -1)), dim=2).reshape(B, 2 * L, H)
         rep = torch.stack((pr, sr), dim=2).reshape(B, 2 * L)
         tgt_len = rep.sum(dim=1)
@@ -147,12 +151,15 @@ class LengthRegulator(nn.Module):
         return self.LR(x, phone_duration, sil_duration, src_lens, max_len)
 
 
-def hip_length_regulate(x, phone, sil, src_lens, max_len, log_domain=False):
-    """torch.ops.flamed_hip.length_regulate (max_len None/0 = the batch's longest utterance)."""
+def hip_length_regulate(x, phone, sil, src_lens, max_len, log_domain=False, exact=False):
+    """torch.ops.flamed_hip.length_regulate (max_len None/0 = the batch's longest utterance); exact:
+    torch.ops.flamed_hip.length_regulate_exact (padded phonemes repeat 0 frames)."""
+    if exact:
+        return ops.length_regulate_exact(x, phone, sil, src_lens, int(max_len) if max_len else 0, bool(log_domain))
     return ops.length_regulate(x, phone, sil, src_lens, int(max_len) if max_len else 0, bool(log_domain))
 
 
-def hip_length_regulate_impl(x, phone, sil, src_lens, max_len, log_domain=False):
+def hip_length_regulate_impl(x, phone, sil, src_lens, max_len, log_domain=False, exact=False):
     """HIP length regulator: phase 1 (repeats + prefix sums), one host read of the lengths (the
     reference's .tolist() sync, pva.py:158), phase 2 (gather)."""
     L_ = nat.lib()
@@ -165,8 +172,9 @@ def hip_length_regulate_impl(x, phone, sil, src_lens, max_len, log_domain=False)
     cum = torch.empty((B, 2 * L + 1), dtype=torch.int64, device=dev)
     tgt = torch.empty((B,), dtype=torch.int64, device=dev)
     st = nat.stream_ptr(dev)
-    nat.check(L_.flamed_lr_lengths(nat.ptr(pf), nat.ptr(sf), nat.ptr(sl), B, L, int(bool(log_domain)), nat.ptr(cum),
-                                   nat.ptr(tgt), st), "flamed_lr_lengths")
+    fn = "flamed_lr_lengths_exact" if exact else "flamed_lr_lengths"
+    nat.check(getattr(L_, fn)(nat.ptr(pf), nat.ptr(sf), nat.ptr(sl), B, L, int(bool(log_domain)), nat.ptr(cum),
+                              nat.ptr(tgt), st), fn)
     T = int(max_len) if max_len else int(tgt.max().item())
     out = torch.empty((B, T, H), dtype=torch.float32, device=dev)
     nat.check(L_.flamed_lr_expand(nat.ptr(xf), nat.ptr(cum), B, L, H, T, nat.ptr(out), st), "flamed_lr_expand")
@@ -200,13 +208,22 @@ class PVA(nn.Module):
         x, _ = self.length_regulator(x, phone_duration, sil_duration, src_len, max_tgt_len)
         return x, losses
 
-    def flow(self, x, src_mask, nfe, temperature):
+    def flow(self, x, src_mask, nfe, temperature, exact=False):
         """Euler loop of both generators (pva.py:97-109); returns final log-durations (dur, sil).
-        Noise: dur then sil from the global CPU RNG, as the reference draws it."""
+        Noise: dur then sil from the global CPU RNG, as the reference draws it.
+        exact (opt-in, no reference counterpart): utterance u of the padded batch, len_u = its count of unmasked
+        phonemes (src_mask is a prefix mask), is flowed as if alone -- over x[u, :len_u] with no mask, from its own
+        slice of the same two draws -- and the returned states are exactly 0 on [len_u, L).  The reference's padded
+        flow lets the two k3 convolutions read the padded rows, whose state stays noise * temperature."""
         b, l, _ = x.size()
         ts = torch.linspace(0, 1, nfe + 1, device=x.device)
         dur_t = torch.randn((b, l)).to(x.device) * temperature
         sil_t = torch.randn((b, l)).to(x.device) * temperature
+        if exact:
+            lens = [int(n) for n in (~src_mask.bool()).sum(-1).tolist()]
+            if _hip_ok(x, self):
+                return ops.pva_flow_exact(self.hip().oid, x, dur_t, sil_t, ts, nfe, lens)
+            return self._flow_each_alone(x, dur_t, sil_t, ts, nfe, lens)
         if _hip_ok(x, self):
             return ops.pva_flow(self.hip().oid, x, src_mask, dur_t, sil_t, ts, nfe)
         delta_t = 1 / nfe
@@ -215,14 +232,27 @@ class PVA(nn.Module):
             sil_t = sil_t + delta_t * self.sil_generator(sil_t, x, ts[i - 1], src_mask)
         return dur_t, sil_t
 
-    def sample(self, x, src_len, src_mask, max_tgt_len=None, nfe=32, temperature=1.0):
-        """reference pva.py:88-116"""
-        dur_t, sil_t = self.flow(x, src_mask, nfe, temperature)
+    def _flow_each_alone(self, x, dur_t, sil_t, ts, nfe, lens):
+        """The exact flow on torch ops: every utterance alone, over its own phonemes, no mask."""
+        delta_t = 1 / nfe
+        dur_o, sil_o = torch.zeros_like(dur_t), torch.zeros_like(sil_t)
+        for u, n in enumerate(lens):
+            xu, d, s = x[u:u + 1, :n], dur_t[u:u + 1, :n], sil_t[u:u + 1, :n]
+            for i in range(1, len(ts)):
+                d = d + delta_t * self.duration_generator(d, xu, ts[i - 1], None)
+                s = s + delta_t * self.sil_generator(s, xu, ts[i - 1], None)
+            dur_o[u, :n], sil_o[u, :n] = d[0], s[0]
+        return dur_o, sil_o
+
+    def sample(self, x, src_len, src_mask, max_tgt_len=None, nfe=32, temperature=1.0, exact=False):
+        """reference pva.py:88-116; exact: flow and LengthRegulator.LR with exact lengths (every utterance's durations
+        and frame count as if alone)."""
+        dur_t, sil_t = self.flow(x, src_mask, nfe, temperature, exact=exact)
         if _lr_hip_ok(x):
-            return self.length_regulator.LR(x, dur_t, sil_t, src_len, max_tgt_len, log_domain=True)
+            return self.length_regulator.LR(x, dur_t, sil_t, src_len, max_tgt_len, log_domain=True, exact=exact)
         phone_duration = torch.clamp(torch.round(torch.exp(dur_t) - 1), min=0)
         sil_duration = torch.clamp(torch.round(torch.exp(sil_t) - 1), min=0)
-        return self.length_regulator(x, phone_duration, sil_duration, src_len, max_tgt_len)
+        return self.length_regulator.LR(x, phone_duration, sil_duration, src_len, max_tgt_len, exact=exact)
 
     def hip_dims_ok(self) -> bool:
         """flamed_dur_create specialises both generators' dims; otherwise the torch ops run."""
@@ -293,7 +323,24 @@ class PvaHIP:
         self._sig = sig
         self._bufs = {}
 
-    def flow(self, x, src_mask, dur_t, sil_t, ts, nfe):
+    def _call_flow(self, enc, mask, d, s, ts, nfe, B, L, ws, use_graph, dev, lens):
+        """flamed_pva_flow, or flamed_pva_flow_exact with the utterances' lengths (the mask is then unused)."""
+        Lb = nat.lib()
+        if lens is None:
+            nat.check(Lb.flamed_pva_flow(self.handles[0], self.handles[1], nat.ptr(enc), nat.ptr(mask), nat.ptr(d),
+                                         nat.ptr(s), nat.ptr(ts), nfe, B, L, nat.ptr(ws), ws.numel(), use_graph,
+                                         nat.stream_ptr(dev)), "flamed_pva_flow")
+            return
+        if len(lens) != B:
+            raise ValueError(f"exact PVA flow: {len(lens)} lengths for a batch of {B}")
+        arr = (ctypes.c_int * B)(*[int(n) for n in lens])
+        nat.check(Lb.flamed_pva_flow_exact(self.handles[0], self.handles[1], nat.ptr(enc), arr, nat.ptr(d), nat.ptr(s),
+                                           nat.ptr(ts), nfe, B, L, nat.ptr(ws), ws.numel(), use_graph,
+                                           nat.stream_ptr(dev)), "flamed_pva_flow_exact")
+
+    def flow(self, x, src_mask, dur_t, sil_t, ts, nfe, lens=None):
+        """lens (exact lengths): B ints, utterance u is flowed over its first lens[u] phonemes as if alone and its
+        states are 0 behind them; src_mask is then not used (None is fine)."""
         dev = x.device
         self._ensure(dev)
         B, L, D = x.shape
@@ -304,9 +351,11 @@ class PvaHIP:
             # directly (the bool mask's bytes are the uint8 the kernel reads) and the states are flowed in
             # place in fresh copies (the op returns new tensors)
             enc = x.float().contiguous()
-            mask = src_mask.contiguous()
-            if mask.dtype not in (torch.bool, torch.uint8):
-                mask = mask.to(torch.uint8)
+            mask = None
+            if lens is None:
+                mask = src_mask.contiguous()
+                if mask.dtype not in (torch.bool, torch.uint8):
+                    mask = mask.to(torch.uint8)
             # contiguous copies: the kernel indexes the states flat (r = b L + l); clone() would keep the
             # strides of a dense non-contiguous input (preserve_format)
             d = dur_t.float().clone(memory_format=torch.contiguous_format)
@@ -314,9 +363,7 @@ class PvaHIP:
             tsc = ts.float().contiguous()
             ws = self.ws.get(Lb.flamed_pva_workspace_size(self.handles[0], B, L, nfe), dev)
             runs0, _ = self.persist_status()
-            nat.check(Lb.flamed_pva_flow(self.handles[0], self.handles[1], nat.ptr(enc), nat.ptr(mask), nat.ptr(d),
-                                         nat.ptr(s), nat.ptr(tsc), nfe, B, L, nat.ptr(ws), ws.numel(), 1,
-                                         nat.stream_ptr(dev)), "flamed_pva_flow")
+            self._call_flow(enc, mask, d, s, tsc, nfe, B, L, ws, 1, dev, lens)
             if not (self.check_persist and not torch.cuda.is_current_stream_capturing()):
                 return d, s
             runs1, _ = self.persist_status()
@@ -329,10 +376,10 @@ class PvaHIP:
             self._fails_seen = fails
             warnings.warn(f"flamed: persistent PVA flow failed ({fails} so far on this pair); "
                           "re-running it on the graph path")
-            return self._graph_flow(x, src_mask, dur_t, sil_t, ts, nfe, 1 | 2)
-        return self._graph_flow(x, src_mask, dur_t, sil_t, ts, nfe, int(bool(self.pva.hip_graph)))
+            return self._graph_flow(x, src_mask, dur_t, sil_t, ts, nfe, 1 | 2, lens)  # (an exact flow is re-run exact)
+        return self._graph_flow(x, src_mask, dur_t, sil_t, ts, nfe, int(bool(self.pva.hip_graph)), lens)
 
-    def _graph_flow(self, x, src_mask, dur_t, sil_t, ts, nfe, use_graph):
+    def _graph_flow(self, x, src_mask, dur_t, sil_t, ts, nfe, use_graph, lens=None):
         dev = x.device
         self._ensure(dev)
         B, L, D = x.shape
@@ -347,15 +394,13 @@ class PvaHIP:
                     "ts": torch.empty((nfe + 1,), dtype=torch.float32, device=dev)}
             self._bufs = {key: bufs}
         bufs["enc"].copy_(x)
-        bufs["mask"].copy_(src_mask)
+        if lens is None:
+            bufs["mask"].copy_(src_mask)
         bufs["dur"].copy_(dur_t)
         bufs["sil"].copy_(sil_t)
         bufs["ts"].copy_(ts)
         ws = self.ws.get(Lb.flamed_pva_workspace_size(self.handles[0], B, L, nfe), dev)
-        nat.check(Lb.flamed_pva_flow(self.handles[0], self.handles[1], nat.ptr(bufs["enc"]), nat.ptr(bufs["mask"]),
-                                     nat.ptr(bufs["dur"]), nat.ptr(bufs["sil"]), nat.ptr(bufs["ts"]), nfe, B, L,
-                                     nat.ptr(ws), ws.numel(), use_graph, nat.stream_ptr(dev)),
-                  "flamed_pva_flow")
+        self._call_flow(bufs["enc"], bufs["mask"], bufs["dur"], bufs["sil"], bufs["ts"], nfe, B, L, ws, use_graph, dev, lens)
         return bufs["dur"].clone(), bufs["sil"].clone()
 
     def persist_status(self):

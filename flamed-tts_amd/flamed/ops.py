@@ -18,6 +18,10 @@ take tensors and scalars only); the registry holds weak references, so a dropped
   flamed_hip::cond_fold_exact(id, cond, mask)                       over its own frames only, as if alone
   flamed_hip::pva_flow(id, x, mask, dur, sil, ts, nfe)  PVA.sample Euler loops       pva.py:97-109
   flamed_hip::length_regulate(x, pd, sd, lens, max_len, log_domain)  LengthRegulator.LR  pva.py:125-166
+  flamed_hip::pva_flow_exact(id, x, dur, sil, ts, nfe, lens)        exact lengths in the prior stage (no reference
+  flamed_hip::length_regulate_exact(x, pd, sd, lens, max_len, log)  counterpart): every utterance flowed over its own
+  flamed_hip::prior_decode_lens(id, x, mask, prompts, P, plens)     phonemes, padded phonemes repeat 0 frames, every
+                                                   utterance decoded behind its own prompt, as if alone
   flamed_hip::fac_decode(id, x, spk)               FACodecDecoder.inference        facodec.py:630-638
   flamed_hip::fac_decode_lens(id, x, spk, lens)    exact lengths (no reference counterpart): every utterance of the
                                                    padded batch decoded over its own frames, as if alone; 0 behind it
@@ -162,6 +166,31 @@ def _(x, phone, sil, src_lens, max_len, log_domain):
     return x.new_empty((B, T, H)), src_lens.new_empty((B,), dtype=torch.int64)
 
 
+@torch.library.custom_op("flamed_hip::pva_flow_exact", mutates_args=())
+def pva_flow_exact(oid: int, x: Tensor, dur_t: Tensor, sil_t: Tensor, ts: Tensor, nfe: int,
+                   lens: List[int]) -> Tuple[Tensor, Tensor]:
+    return owner(oid).flow(x, None, dur_t, sil_t, ts, nfe, lens=lens)
+
+
+@pva_flow_exact.register_fake
+def _(oid, x, dur_t, sil_t, ts, nfe, lens):
+    return (dur_t.new_empty(dur_t.shape, dtype=torch.float32), sil_t.new_empty(sil_t.shape, dtype=torch.float32))
+
+
+@torch.library.custom_op("flamed_hip::length_regulate_exact", mutates_args=())
+def length_regulate_exact(x: Tensor, phone: Tensor, sil: Tensor, src_lens: Tensor, max_len: int,
+                          log_domain: bool) -> Tuple[Tensor, Tensor]:
+    from .models.synthesizer.pva import hip_length_regulate_impl
+    return hip_length_regulate_impl(x, phone, sil, src_lens, max_len, log_domain, exact=True)
+
+
+@length_regulate_exact.register_fake
+def _(x, phone, sil, src_lens, max_len, log_domain):
+    B, _, H = x.shape
+    T = max_len if max_len else torch.library.get_ctx().new_dynamic_size()
+    return x.new_empty((B, T, H)), src_lens.new_empty((B,), dtype=torch.int64)
+
+
 # ---------------------------------------------------------------- FaCodec
 
 @torch.library.custom_op("flamed_hip::fac_decode", mutates_args=())
@@ -238,5 +267,20 @@ def _(oid, x, tgt_mask, prompts, prompts_len):
     return x.new_empty((B, nq, T, D)), x.new_empty((B, V1, nq, T))
 
 
+@torch.library.custom_op("flamed_hip::prior_decode_lens", mutates_args=())
+def prior_decode_lens(oid: int, x: Tensor, tgt_mask: Tensor, prompts: Tensor, prompts_len: int,
+                      prompt_lens: List[int]) -> Tuple[Tensor, Tensor]:
+    return owner(oid).decode(x, tgt_mask, prompts, prompts_len, prompt_lens=prompt_lens)
+
+
+@prior_decode_lens.register_fake
+def _(oid, x, tgt_mask, prompts, prompts_len, prompt_lens):
+    B, T, _ = x.shape
+    pg = owner(oid).pg
+    nq, D, V1 = len(pg.prior_decoder), pg.shared_decoder.d_model, pg.head.weight.shape[0]
+    return x.new_empty((B, nq, T, D)), x.new_empty((B, V1, nq, T))
+
+
 OPS = ("den_velocity", "den_solve", "den_solve_rk2", "den_solve_lens", "den_solve_rk2_lens", "cond_fold", "cond_fold_exact",
-       "pva_flow", "length_regulate", "fac_decode", "fac_decode_lens", "enc_encode", "vq_encode", "prior_encode", "prior_decode")
+       "pva_flow", "length_regulate", "fac_decode", "fac_decode_lens", "enc_encode", "vq_encode", "prior_encode", "prior_decode",
+       "pva_flow_exact", "length_regulate_exact", "prior_decode_lens")

@@ -192,16 +192,22 @@ class RtfMeter:
         return sum(d * SR / HOP for d in self.durations) / total if total > 0 else float("nan")
 
 
-def _solver_suffix(solver_denoiser: str, exact_lengths: bool = False) -> str:
-    return ("" if solver_denoiser == "euler" else f"-{solver_denoiser}") + ("-exact" if exact_lengths else "")
+def _solver_suffix(solver_denoiser: str, exact_lengths: bool = False, exact_prior: bool = False) -> str:
+    return (("" if solver_denoiser == "euler" else f"-{solver_denoiser}") + ("-exact" if exact_lengths else "") +
+            ("-xprior" if exact_prior else ""))
+
+
+def _prior_kw(exact_prior: bool) -> dict:
+    """The flag travels only when set, so a model without it keeps working with the default."""
+    return {"exact_prior": True} if exact_prior else {}
 
 
 def synthesize_with_prompts(model: Flamed, codec_encoder, codec_decoder, text: str, prompt_dir: str,
                             prompt_list: List[str], output_dir: str, nsteps_durgen: int, nsteps_denoiser: int,
                             temp_durgen: float, temp_denoiser: float, meter: Optional[RtfMeter] = None,
-                            solver_denoiser: str = "euler", exact_lengths: bool = False):
+                            solver_denoiser: str = "euler", exact_lengths: bool = False, exact_prior: bool = False):
     """One `Flamed.sample` per prompt (reference :194-217).  A denoiser solver other than Euler is appended to the
-    output names, so runs with different solvers do not overwrite each other; so is `-exact` for exact lengths."""
+    output names, so runs with different solvers do not overwrite each other; so are `-exact` for exact lengths and `-xprior` for the exact prior stage."""
     os.makedirs(output_dir, exist_ok=True)
     meter = meter if meter is not None else RtfMeter()
     rank, world, _ = fdist.dist_env()
@@ -210,10 +216,10 @@ def synthesize_with_prompts(model: Flamed, codec_encoder, codec_decoder, text: s
         res = model.sample(text=text, prompt_raw=audio_prompt, sr=SR, codec_encoder=codec_encoder,
                            codec_decoder=codec_decoder, nsteps_durgen=nsteps_durgen, nsteps_denoiser=nsteps_denoiser,
                            temp_durgen=temp_durgen, temp_denoiser=temp_denoiser, solver_denoiser=solver_denoiser,
-                           exact_lengths=exact_lengths)
+                           exact_lengths=exact_lengths, **_prior_kw(exact_prior))
         meter.add(res["time"], len(res["wav"]))
         stem = os.path.splitext(os.path.basename(prompt_name))[0]
-        out_name = f"{stem}-{nsteps_durgen}-{nsteps_denoiser}-{temp_durgen}-{temp_denoiser}{_solver_suffix(solver_denoiser, exact_lengths)}.wav"
+        out_name = f"{stem}-{nsteps_durgen}-{nsteps_denoiser}-{temp_durgen}-{temp_denoiser}{_solver_suffix(solver_denoiser, exact_lengths, exact_prior)}.wav"
         write_wav(os.path.join(output_dir, out_name), res["wav"], SR)
     return meter.rtf()
 
@@ -222,14 +228,16 @@ def synthesize_with_metadata(model: Flamed, codec_encoder, codec_decoder, metada
                              output_dir: str, nsteps_durgen: int, nsteps_denoiser: int, temp_durgen: float,
                              temp_denoiser: float, skip_existing: bool, batch_size: int,
                              meter: Optional[RtfMeter] = None, solver_denoiser: str = "euler",
-                             exact_lengths: bool = False):
+                             exact_lengths: bool = False, exact_prior: bool = False):
     """Batched `Flamed.sample_batch` over a `target|prompt|text` file (reference :220-303).  A denoiser solver
     other than Euler is appended to the target directory's name, and `-exact` for exact lengths (every utterance of
     a padded batch then gets the latents and the waveform it would get alone, and its file is trimmed to its own
-    length, out["wav_lens"]; without the flag every file of a batch has the batch's padded length)."""
+    length, out["wav_lens"]; without the flag every file of a batch has the batch's padded length), and `-xprior` for
+    the exact prior stage (durations, frame counts and prior embeddings as if alone; the prompts' own lengths are
+    read from the pad id that build_metadata_batch pads them with)."""
     with open(metadata_file, "r", encoding="utf-8") as fin:
         entries = [line.strip() for line in fin if line.strip()]
-    target_dir = os.path.join(output_dir, f"nfe{nsteps_denoiser}-temp{temp_denoiser}{_solver_suffix(solver_denoiser, exact_lengths)}")
+    target_dir = os.path.join(output_dir, f"nfe{nsteps_denoiser}-temp{temp_denoiser}{_solver_suffix(solver_denoiser, exact_lengths, exact_prior)}")
     os.makedirs(target_dir, exist_ok=True)
     meter = meter if meter is not None else RtfMeter()
     cache: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
@@ -257,7 +265,7 @@ def synthesize_with_metadata(model: Flamed, codec_encoder, codec_decoder, metada
         out = model.sample_batch(phonemes=phonemes, src_lens=src_lens, prompts=prompts, timbres=timbres,
                                  codec_decoder=codec_decoder, temp_durgen=temp_durgen, temp_denoiser=temp_denoiser,
                                  nsteps_durgen=nsteps_durgen, nsteps_denoiser=nsteps_denoiser,
-                                 solver_denoiser=solver_denoiser, exact_lengths=exact_lengths)
+                                 solver_denoiser=solver_denoiser, exact_lengths=exact_lengths, **_prior_kw(exact_prior))
         per_sample = out["time"] / len(batch)
         wav_lens = out["wav_lens"].tolist() if "wav_lens" in out else [None] * len(batch)
         for item, wav_t, n in zip(batch, out["wav"], wav_lens):
@@ -312,6 +320,11 @@ def build_arg_parser():
                    help="Fold, solve and decode every utterance of a padded batch over its own frames only, so its "
                         "latents and its waveform do not depend on the batch it shares, and write each file of "
                         "--metadata-file mode trimmed to its own length (default: False, the reference's padded batch).")
+    p.add_argument("--exact-prior", type=str2bool, default=False,
+                   help="Run the prior stage (duration flow, length regulator, prior decoders) for every utterance of a "
+                        "padded batch over its own phonemes and behind its own prompt, so its durations, its frame "
+                        "count and its prior embeddings do not depend on the batch it shares; with --exact-lengths a "
+                        "file no longer depends on the other lines of its batch (default: False).")
     p.add_argument("--temp-durgen", type=float, default=0.3, help="Duration generator temperature.")
     p.add_argument("--temp-denoiser", type=float, default=0.3, help="Denoiser temperature.")
     p.add_argument("--device", type=str, default="cuda:0", help="Device to run inference on.")
@@ -348,7 +361,8 @@ def main(args: Optional[argparse.Namespace] = None):
                   output_dir=args.output_dir, nsteps_durgen=args.nsteps_durgen, nsteps_denoiser=args.nsteps_denoiser,
                   temp_durgen=args.temp_durgen, temp_denoiser=args.temp_denoiser, meter=meter,
                   solver_denoiser=getattr(args, "solver_denoiser", "euler"),
-                  exact_lengths=bool(getattr(args, "exact_lengths", False)))
+                  exact_lengths=bool(getattr(args, "exact_lengths", False)),
+                  exact_prior=bool(getattr(args, "exact_prior", False)))
     if args.metadata_file:
         rtf = synthesize_with_metadata(metadata_file=args.metadata_file, skip_existing=args.skip_existing,
                                        batch_size=args.batch_size, **common)

@@ -326,6 +326,17 @@ FLAMED_API size_t flamed_pva_workspace_size(flamed_dur_t h, int B, int L, int nf
 FLAMED_API int flamed_pva_flow(flamed_dur_t dur, flamed_dur_t sil, const float* enc, const uint8_t* mask, float* dur_t,
                                float* sil_t, const float* ts, int nfe, int B, int L, void* ws, size_t ws_bytes,
                                int use_graph, hipStream_t stream);
+/* Exact lengths (no reference counterpart): the same flow with every utterance of the padded batch flowed as if
+ * alone.  lens: B HOST ints, 1 <= lens[u] <= L (copied at the call; utterance u owns rows [u L, u L + lens[u])).
+ * Both convolutions' windows end at the utterance's own end, rows behind it are neither read (enc, dur_t and sil_t
+ * may hold anything there, NaN included) nor relied on, and dur_t / sil_t are exactly 0 there on return; a failed
+ * persistent launch NaN-poisons valid rows only.  No mask is read.  use_graph as in flamed_pva_flow: an eligible flow
+ * (B*L <= 640) is the one persistent launch (the kernel's exact-lengths instantiation), the graph path keeps a
+ * cached graph of its own, so dense and exact calls do not evict each other.  All lens[u] == L gives the bits of
+ * flamed_pva_flow with an all-zero mask. */
+FLAMED_API int flamed_pva_flow_exact(flamed_dur_t dur, flamed_dur_t sil, const float* enc, const int* lens, float* dur_t,
+                                     float* sil_t, const float* ts, int nfe, int B, int L, void* ws, size_t ws_bytes,
+                                     int use_graph, hipStream_t stream);
 /* 1 when a flamed_pva_flow(use_graph != 0) of B x L rows on this pair, on `stream` (its capture state
  * counts), would run as the persistent launch (the caller may then pass its own buffers: no graph keyed on
  * their addresses), 0 otherwise. */
@@ -342,6 +353,10 @@ FLAMED_API int flamed_pva_persist_status(flamed_dur_t dur, int* runs, int* fails
  * (then clamp(round(exp(d) - 1), 0) is applied first, pva.py:111-112).  src_lens: int64 B. */
 FLAMED_API int flamed_lr_lengths(const float* phone, const float* sil, const int64_t* src_lens, int B, int L,
                                  int log_domain, int64_t* cum, int64_t* tgt_len, hipStream_t stream);
+/* Exact lengths: flamed_lr_lengths with padding phonemes repeating 0 frames (not 1), so tgt_len[b] is the length
+ * utterance b has alone; flamed_lr_expand takes the result unchanged. */
+FLAMED_API int flamed_lr_lengths_exact(const float* phone, const float* sil, const int64_t* src_lens, int B, int L,
+                                       int log_domain, int64_t* cum, int64_t* tgt_len, hipStream_t stream);
 /* Phase 2 (after the host has read max(tgt_len), as the reference's .tolist() does): gather frames
  * out[b][f] = x[b][src] (silence frames copy phoneme 0), zero beyond tgt_len[b], truncated at T_out. */
 FLAMED_API int flamed_lr_expand(const float* x, const int64_t* cum, int B, int L, int H, int T_out, float* out,
@@ -447,6 +462,13 @@ FLAMED_API int flamed_prior_encode(flamed_prior_t h, const int64_t* texts, const
 FLAMED_API int flamed_prior_decode(flamed_prior_t h, const float* x, const uint8_t* tgt_mask, const int64_t* prompts,
                                    int B, int T, int P, const float* pos, float* embs, float* logits, void* ws,
                                    size_t ws_bytes, int use_graph, hipStream_t stream);
+/* flamed_prior_decode with per-utterance prompt lengths (no reference counterpart): prompt_lens: B HOST ints,
+ * 0 <= prompt_lens[u] <= P (copied at the call); utterance u's prompt is prompts[u, :, :prompt_lens[u]], the slots
+ * behind it are never read.  Each utterance is decoded as if alone: its keys are its own prompt and its own frames,
+ * target frame t sits at position prompt_lens[u] + t.  prompt_lens NULL, or every length == P: the dense call itself. */
+FLAMED_API int flamed_prior_decode_lens(flamed_prior_t h, const float* x, const uint8_t* tgt_mask, const int64_t* prompts,
+                                        int B, int T, int P, const int* prompt_lens, const float* pos, float* embs,
+                                        float* logits, void* ws, size_t ws_bytes, int use_graph, hipStream_t stream);
 /* Operand type of the decoder-side GEMMs (bridge, shared decoder, per-quantizer decoders, head):
  * FLAMED_F32 (the C default: exact fp32 MFMA) or FLAMED_BF16 (bf16 operands, fp32 accumulation; the weights
  * are converted once on the first bf16 decode).  The encoder always runs fp32 (it feeds the durations).
