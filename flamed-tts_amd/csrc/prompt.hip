@@ -10,6 +10,7 @@
 //     :49-51), last LayerNorm, mean over time (facodec.py:530-532).
 // Exact fp32 (codes must match the reference's argmax; f32 MFMA GEMMs are fp32 FMA chains).
 #include "flamed_hip.h"
+#include "flamed_diag.h"
 #include "gemm.hpp"
 #include "xfmr.hpp"
 
@@ -154,14 +155,24 @@ __global__ void timbre_in_kernel(const float* __restrict__ x, const float* __res
   X[((size_t)b * T + t) * C + c] = x[i] + pe[(size_t)b * C + c];
 }
 
-// mean over time of the last-LayerNorm rows (facodec.py:531-532): spk[b][c] = sum_t Y[b][t][c] / T.
-__global__ void mean_t_kernel(const float* __restrict__ Y, int B, int T, int C, float* __restrict__ spk) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * C) return;
-  int b = i / C, c = i - b * C;
-  float s = 0.f;
-  for (int t = 0; t < T; ++t) s += Y[((size_t)b * T + t) * C + c];
-  spk[i] = s / (float)T;
+// mean over time of the last-LayerNorm rows (facodec.py:531-532): spk[b][c] = sum_t Y[b][t][c] / T.  One workgroup
+// per (64 channels, utterance); wave w sums the frames t = w (mod 8) and wave 0 adds the eight partials in wave
+// order.  The sums are held in fp64: one fp32 running sum over T frames drifts by about sqrt(T / 3) roundings, which
+// from a few hundred frames on is several times the error of the reference's pairwise fp32 mean.
+constexpr int kMeanWaves = 8;
+__global__ __launch_bounds__(64 * kMeanWaves) void mean_t_kernel(const float* __restrict__ Y, int T, int C,
+                                                                 float* __restrict__ spk) {
+  __shared__ double part[kMeanWaves][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + lane, b = blockIdx.y;
+  double s = 0.0;
+  if (c < C)
+    for (int t = w; t < T; t += kMeanWaves) s += (double)Y[((size_t)b * T + t) * C + c];
+  part[w][lane] = s;
+  __syncthreads();
+  if (w != 0 || c >= C) return;
+  for (int u = 1; u < kMeanWaves; ++u) s += part[u][lane];
+  spk[(size_t)b * C + c] = (float)(s / (double)T);
 }
 
 __global__ void vq_taps_kernel(const float* __restrict__ src, float* __restrict__ dst, int N, int Cin, int KT) {
@@ -235,7 +246,7 @@ static int run_vq(PromptVq* p, const float* x, int B, int T, float* outs, int64_
     std::swap(X, R);
   }
   if ((rc = ln_mask(d, X, p->lg, p->lb, nullptr, w.H, M, T, nullptr, 0, 0, 0, 0, st))) return rc;
-  hipLaunchKernelGGL(mean_t_kernel, dim3((B * d + 255) / 256), dim3(256), 0, st, w.H, B, T, d, spk);
+  hipLaunchKernelGGL(mean_t_kernel, dim3((d + 63) / 64, B), dim3(64 * kMeanWaves), 0, st, w.H, T, d, spk);
   FL_LAUNCH_CHECK();
   return kOk;
 }
@@ -374,6 +385,19 @@ FLAMED_API int flamed_vq_load(flamed_vq_t h, const float* const* w, int nw, hipS
 FLAMED_API size_t flamed_vq_workspace_size(flamed_vq_t h, int B, int T) {
   PromptVq* p = reinterpret_cast<PromptVq*>(h);
   return p ? vq_ws_layout(p, B, T, nullptr, nullptr) : 0;
+}
+
+// Diagnostic (include/flamed_diag.h): byte offsets of the flamed_vq_encode workspace's buffers X, R, H, QKV, O, Hf
+// (vq_ws_layout).  After an encode H holds the last-LayerNorm rows (B*T, d) that mean_t_kernel averages.
+FLAMED_API int flamed_vq_ws_offsets(flamed_vq_t h, int B, int T, size_t* off) {
+  PromptVq* p = reinterpret_cast<PromptVq*>(h);
+  FL_REQUIRE(p && off && B > 0 && T > 0, "flamed_vq_ws_offsets: bad args");
+  char* const base = reinterpret_cast<char*>(4096);  // any non-null base: offsets are relative to it
+  VqWs w;
+  vq_ws_layout(p, B, T, base, &w);
+  const float* q[6] = {w.X, w.R, w.H, w.QKV, w.O, w.Hf};
+  for (int i = 0; i < 6; ++i) off[i] = (size_t)((const char*)q[i] - base);
+  return kOk;
 }
 
 FLAMED_API int flamed_vq_encode(flamed_vq_t h, const float* x, int B, int T, float* outs, int64_t* codes, float* qbuf,

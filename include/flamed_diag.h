@@ -71,6 +71,9 @@ FLAMED_API int flamed_den_persist_fails(flamed_den_t h, int* fails);
 /* Byte offsets inside the flamed_den_velocity / flamed_den_step workspace of its buffers X, S0, S1, D, U, GP, GNS,
  * Y, SL, A16, XA, XP (off[12]; SIZE_MAX = absent at this B, T) under the handle's current knobs. */
 FLAMED_API int flamed_den_ws_offsets(flamed_den_t h, int B, int T, size_t* off);
+/* Byte offsets inside the flamed_vq_encode workspace of its buffers X, R, H, QKV, O, Hf (off[6]).  After an encode H
+ * holds the timbre encoder's last-LayerNorm rows (B*T, hidden) whose mean over time is the speaker embedding. */
+FLAMED_API int flamed_vq_ws_offsets(flamed_vq_t h, int B, int T, size_t* off);
 /* The persistent solve's reset-prologue ticket arithmetic, host-side (no GPU): the arrival count `*target` that
  * completes the launch of `ticket` (a fetch_add result), and whether counter value `cur` has reached it
  * (wrap-safe across 2^32). */
