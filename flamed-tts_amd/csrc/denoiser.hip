@@ -16,6 +16,7 @@
 #include "gemm.hpp"
 #include "gemm_dma.hpp"
 #include "gemm_8p.hpp"
+#include "graph.hpp"
 #include "persist.hpp"
 
 #include <mutex>
@@ -3074,49 +3075,40 @@ static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe
     if (br) {  // tune split_graph 1 (round 4): one graph, the chains as parallel branches (fork / join events)
       for (int k = 1; k < S; ++k)
         if (!d->cap_aux[k]) FL_HIP(hipStreamCreateWithFlags(&d->cap_aux[k], hipStreamNonBlocking));
-      FL_HIP(hipStreamBeginCapture(d->cap_stream, hipStreamCaptureModeRelaxed));
-      FL_HIP(hipEventRecord(d->cap_ev[0], d->cap_stream));
-      for (int k = 1; k < S; ++k) FL_HIP(hipStreamWaitEvent(d->cap_aux[k], d->cap_ev[0], 0));
-      int rc = kOk;
-      for (int k = 0; k < S && rc == kOk; ++k) {
-        float* xk; const float* mk; void* wk;
-        sub(k, xk, mk, wk);
-        hipStream_t cs = k == 0 ? d->cap_stream : d->cap_aux[k];
-        for (int s = 0; s < G && rc == kOk; ++s)
-          rc = rk ? rk_eval(s, k, nullptr, cs, d->ctr + 16 * k)
-                  : den_step(d, xk, mk, T, Bk, T, dt, nullptr, wk, cs, d->ctr + 16 * k, fbig ? xk : nullptr, B, k, S);
-      }
-      for (int k = 1; k < S && rc == kOk; ++k) {
-        FL_HIP(hipEventRecord(d->cap_ev[k], d->cap_aux[k]));
-        FL_HIP(hipStreamWaitEvent(d->cap_stream, d->cap_ev[k], 0));
-      }
-      hipGraph_t g = nullptr;
-      hipError_t e = hipStreamEndCapture(d->cap_stream, &g);
-      if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-      FL_HIP(e);
-      hipError_t ie = hipGraphInstantiate(&d->gexec, g, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(g);
-      FL_HIP(ie);
+      const int crc = capture_exec(d->cap_stream, &d->gexec, [&](hipStream_t cap) -> int {
+        FL_HIP(hipEventRecord(d->cap_ev[0], cap));
+        for (int k = 1; k < S; ++k) FL_HIP(hipStreamWaitEvent(d->cap_aux[k], d->cap_ev[0], 0));
+        int rc = kOk;
+        for (int k = 0; k < S && rc == kOk; ++k) {
+          float* xk; const float* mk; void* wk;
+          sub(k, xk, mk, wk);
+          hipStream_t cs = k == 0 ? cap : d->cap_aux[k];
+          for (int s = 0; s < G && rc == kOk; ++s)
+            rc = rk ? rk_eval(s, k, nullptr, cs, d->ctr + 16 * k)
+                    : den_step(d, xk, mk, T, Bk, T, dt, nullptr, wk, cs, d->ctr + 16 * k, fbig ? xk : nullptr, B, k, S);
+        }
+        for (int k = 1; k < S && rc == kOk; ++k) {
+          FL_HIP(hipEventRecord(d->cap_ev[k], d->cap_aux[k]));
+          FL_HIP(hipStreamWaitEvent(cap, d->cap_ev[k], 0));
+        }
+        return rc;
+      });
+      if (crc) return crc;
     }
     // one graph per chain (G steps of its sub-batch), captured one after another on cap_stream
     for (int k = 0; k < (br ? 0 : S); ++k) {
-      FL_HIP(hipStreamBeginCapture(d->cap_stream, hipStreamCaptureModeRelaxed));
-      int rc = kOk;
-      float* xk; const float* mk; void* wk;
-      sub(k, xk, mk, wk);
-      for (int s = 0; s < G && rc == kOk; ++s) {
-        if (rk) rc = rk_eval(s, k, nullptr, d->cap_stream, d->ctr + 16 * k);
-        else if (fused) rc = den_step(d, s % 2 ? w.XP : xt, mods, T, B, T, dt, nullptr, ws, d->cap_stream, d->ctr, s % 2 ? xt : w.XP);
-        else rc = den_step(d, xk, mk, T, Bk, T, dt, nullptr, wk, d->cap_stream, d->ctr + 16 * k, fbig ? xk : nullptr, B, k, S);
-      }
-      hipGraph_t g = nullptr;
-      hipError_t e = hipStreamEndCapture(d->cap_stream, &g);
-      if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-      FL_HIP(e);
-      hipGraphExec_t& ex = k == 0 ? d->gexec : d->gexec_c[k];
-      hipError_t ie = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(g);
-      FL_HIP(ie);
+      const int crc = capture_exec(d->cap_stream, k == 0 ? &d->gexec : &d->gexec_c[k], [&](hipStream_t cap) -> int {
+        int rc = kOk;
+        float* xk; const float* mk; void* wk;
+        sub(k, xk, mk, wk);
+        for (int s = 0; s < G && rc == kOk; ++s) {
+          if (rk) rc = rk_eval(s, k, nullptr, cap, d->ctr + 16 * k);
+          else if (fused) rc = den_step(d, s % 2 ? w.XP : xt, mods, T, B, T, dt, nullptr, ws, cap, d->ctr, s % 2 ? xt : w.XP);
+          else rc = den_step(d, xk, mk, T, Bk, T, dt, nullptr, wk, cap, d->ctr + 16 * k, fbig ? xk : nullptr, B, k, S);
+        }
+        return rc;
+      });
+      if (crc) return crc;
     }
     d->g_B = B; d->g_T = T; d->g_nfe = nfe; d->g_epoch = d->tune_ver; d->g_xt = xt; d->g_mods = mods; d->g_ws = ws;
     d->g_a = rk ? rk->a : 0.0;
@@ -3311,22 +3303,18 @@ FLAMED_API int flamed_den_time_kernels_graph(flamed_den_t h, float* xt, const fl
     FL_LAUNCH_CHECK();
   }
   auto timed = [&](int dup, float* ms) -> int {
-    d->tune.dup_class = dup;
-    FL_HIP(hipStreamBeginCapture(d->cap_stream, hipStreamCaptureModeRelaxed));
-    int rc = kOk;
-    for (int i = 0; i < kSteps && rc == kOk; ++i) {
-      if (fused) rc = den_step(d, i % 2 ? w.XP : xt, mods, T, B, T, 0.f, nullptr, ws, d->cap_stream, nullptr, i % 2 ? xt : w.XP);
-      else rc = den_step(d, xt, mods, T, B, T, 0.f, nullptr, ws, d->cap_stream, nullptr, fbig ? xt : nullptr);
-    }
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(d->cap_stream, &g);
-    d->tune.dup_class = saved_dup;
-    if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-    FL_HIP(e);
     hipGraphExec_t ex;
-    hipError_t ie = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    FL_HIP(ie);
+    const int crc = capture_exec(d->cap_stream, &ex, [&](hipStream_t cap) -> int {
+      d->tune.dup_class = dup;
+      int rc = kOk;
+      for (int i = 0; i < kSteps && rc == kOk; ++i) {
+        if (fused) rc = den_step(d, i % 2 ? w.XP : xt, mods, T, B, T, 0.f, nullptr, ws, cap, nullptr, i % 2 ? xt : w.XP);
+        else rc = den_step(d, xt, mods, T, B, T, 0.f, nullptr, ws, cap, nullptr, fbig ? xt : nullptr);
+      }
+      d->tune.dup_class = saved_dup;
+      return rc;
+    });
+    if (crc) return crc;
     FL_HIP(hipGraphLaunch(ex, st));
     FL_HIP(hipGraphLaunch(ex, st));
     FL_HIP(hipEventRecord(e0, st));

@@ -13,6 +13,7 @@
 // pva.py:111-112), builds the interleaved phone/silence repeat prefix sums, and gathers the frames.
 #include "flamed_hip.h"
 #include "gemm.hpp"
+#include "graph.hpp"
 #include "lens.hpp"
 #include "pvaflow.hpp"
 
@@ -56,25 +57,13 @@ __global__ void split_proj_kernel(const float* __restrict__ src, float* __restri
 }
 
 // Exact lengths (flamed_pva_flow_exact): utterance u of the padded batch owns rows [u L, u L + lens[u]).  A conv
-// window is cut at that end instead of at L, and a row behind it gathers nothing; the dense loaders (EX = false)
-// carry no length and are the loaders they always were.
-template <bool EX>
-struct DurLens {
-  __device__ int len(int, int L) const { return L; }
-};
-template <>
-struct DurLens<true> {
-  const int* __restrict__ lens;  // B device ints (handle-owned, filled stream-ordered per call)
-  __device__ int len(int m, int L) const {
-    const int n = lens[m / L];
-    return n < 0 ? 0 : (n < L ? n : L);
-  }
-};
+// window is cut at that end instead of at L, and a row behind it gathers nothing (lens.hpp: SeqEnd<true>, one row per
+// length unit); the dense loaders carry no length and are the loaders they always were.
 
 // conv1 A operand: out0[src] = P[src] + w0 * xt[src] + temb (zero outside the utterance).  With a
 // device step counter `ctr` the time-embedding row is temb + (*ctr) * Cin (graph replay).
-template <bool EX>
-struct LoadDurInT : DurLens<EX> {
+template <class End = SeqEnd<false>>
+struct LoadDurInT {
   const float* __restrict__ P;
   const float* __restrict__ w0;
   const float* __restrict__ xt;
@@ -82,16 +71,17 @@ struct LoadDurInT : DurLens<EX> {
   int Cin;
   int L;
   const int* __restrict__ ctr;
+  [[no_unique_address]] End end;
   struct Raw { float v[4]; };
   static constexpr int stat_rows(int) { return 0; }
   __device__ void prologue(int, int, int, float*) const {}
   __device__ Raw issue(int m, int k) const {
     Raw r;
     int tap = k / Cin, c = k - tap * Cin;
-    const int lm = m % L, Lr = this->len(m, L);
+    const int lm = m % L, Lr = end.end(m / L, L);
     int l = lm + tap - 1;
     bool out = l < 0 || l >= Lr;
-    if constexpr (EX) out = out || lm >= Lr;
+    if constexpr (End::kExact) out = out || lm >= Lr;
     if (out) {
       r.v[0] = r.v[1] = r.v[2] = r.v[3] = 0.f;
       return r;
@@ -108,30 +98,6 @@ struct LoadDurInT : DurLens<EX> {
   }
   template <typename D> __device__ u32x4 finish(const Raw& r, int, int, const float*, int) const { return pack_chunk<D>(r.v); }
 };
-using LoadDurIn = LoadDurInT<false>;
-
-// conv2's A operand with exact lengths: LoadConvRows<float, true> (LayerNorm_1 of the tap rows), the window cut at the
-// end of the row's own utterance.
-struct LoadConvRowsLens {
-  LoadConvRows<float, true> base;
-  DurLens<true> dl;
-  using Raw = LoadConvRows<float, true>::Raw;
-  static constexpr int stat_rows(int BM) { return LoadConvRows<float, true>::stat_rows(BM); }
-  __device__ void prologue(int bm, int BM, int M, float* st) const { base.prologue(bm, BM, M, st); }
-  __device__ Raw issue(int m, int k) const {
-    const int L = base.L, lm = m % L, Lr = dl.len(m, L);
-    const int l = lm + (k / base.Cin - base.KT / 2) * base.dil;
-    if (lm >= Lr || l < 0 || l >= Lr) {
-      Raw r;
-      r.src = -1;
-      return r;
-    }
-    return base.issue(m, k);
-  }
-  template <typename D> __device__ u32x4 finish(const Raw& r, int m, int k, const float* st, int bm) const {
-    return base.template finish<D>(r, m, k, st, bm);
-  }
-};
 
 // the head's padding test: the mask byte (dense), or the row's place in its own utterance (exact lengths: a row
 // behind the end is written as 0 and never read)
@@ -141,10 +107,10 @@ struct HeadMask {
   __device__ bool pad(int m) const { return mask[m] != 0; }
 };
 struct HeadLens {
-  DurLens<true> dl;
+  SeqEnd<true> end;
   int L;
   static constexpr bool kExact = true;
-  __device__ bool pad(int m) const { return m % L >= dl.len(m, L); }
+  __device__ bool pad(int m) const { return m % L >= end.end(m / L, L); }
 };
 
 // LN2 + Linear(F->1) + masked_fill(mask, 0) + Euler update; one wave per row.
@@ -286,34 +252,28 @@ static int net_prepare(DurNet* n, const float* enc, int M, const float* ts, int 
 struct NetBufs {
   float *R1, *S1, *R2;
 };
+// One Euler step of one net.  End = SeqEnd<true>: the same three launches, windows and head cut at every utterance's
+// own end (`mask` is then null and never read).
+template <class End>
 static int net_step(DurNet* n, const float* P, const float* temb, float* xt, const uint8_t* mask, int B, int L, float dt,
-                    const NetBufs& w, hipStream_t st, const int* ctr = nullptr, int* ctr_inc = nullptr,
-                    bool split = true, const int* lens = nullptr) {
+                    const NetBufs& w, hipStream_t st, const int* ctr, int* ctr_inc, bool split, End end) {
   const int M = B * L, D = n->D, F = n->F;
   const int NT = F / 64;
   SplitScope split_scope(split && n->split_mem && tune_snapshot_pva_split() ? &n->split : nullptr);
   int rc;
-  if (lens) {  // exact lengths: the same three launches, windows and head cut at every utterance's own end
-    if ((rc = launch_gemm_auto<float>(pick_cfg(M) == kCfgSmall ? kCfgSmall : kCfgMid,
-                                      LoadDurInT<true>{{lens}, P, n->w0, xt, temb, D, L, ctr}, n->c1w, 3 * D,
-                                      EpiBiasStatsT<true>{n->c1b, w.R1, F, w.S1, NT}, M, F, 3 * D, st)))
-      return rc;
-    if ((rc = launch_gemm<float>(LoadConvRowsLens{{w.R1, F, L, 3, 1, w.S1, NT, 64, 1e-5f, n->g1, n->b1}, {lens}}, n->c2w, 3 * F,
-                                 EpiBiasAct<float, 3>{n->c2b, w.R2, F}, M, F, 3 * F, st)))
-      return rc;
-    hipLaunchKernelGGL((dur_head_kernel<384, HeadLens>), dim3((M + 3) / 4), dim3(256), 0, st, w.R2, n->g2, n->b2, n->lw, n->lb,
-                       HeadLens{{lens}, L}, xt, M, dt, ctr_inc);
-    FL_LAUNCH_CHECK();
-    return kOk;
-  }
-  if ((rc = launch_gemm_auto<float>(pick_cfg(M) == kCfgSmall ? kCfgSmall : kCfgMid, LoadDurIn{{}, P, n->w0, xt, temb, D, L, ctr}, n->c1w, 3 * D,
-                                          EpiBiasStatsT<true>{n->c1b, w.R1, F, w.S1, NT}, M, F, 3 * D, st)))
+  if ((rc = launch_gemm_auto<float>(pick_cfg(M) == kCfgSmall ? kCfgSmall : kCfgMid,
+                                    LoadDurInT<End>{P, n->w0, xt, temb, D, L, ctr, end}, n->c1w, 3 * D,
+                                    EpiBiasStatsT<true>{n->c1b, w.R1, F, w.S1, NT}, M, F, 3 * D, st)))
     return rc;
-  if ((rc = launch_gemm<float>(LoadConvRows<float, true>{w.R1, F, L, 3, 1, w.S1, NT, 64, 1e-5f, n->g1, n->b1}, n->c2w,
-                                          3 * F, EpiBiasAct<float, 3>{n->c2b, w.R2, F}, M, F, 3 * F, st)))
+  if ((rc = launch_gemm<float>(LoadConvRows<float, true, End>{w.R1, F, L, 3, 1, w.S1, NT, 64, 1e-5f, n->g1, n->b1, end}, n->c2w,
+                               3 * F, EpiBiasAct<float, 3>{n->c2b, w.R2, F}, M, F, 3 * F, st)))
     return rc;
-  hipLaunchKernelGGL((dur_head_kernel<384, HeadMask>), dim3((M + 3) / 4), dim3(256), 0, st, w.R2, n->g2, n->b2, n->lw, n->lb,
-                     HeadMask{mask}, xt, M, dt, ctr_inc);
+  auto head = [&] {
+    if constexpr (End::kExact) return HeadLens{end, L};
+    else return HeadMask{mask};
+  }();
+  hipLaunchKernelGGL((dur_head_kernel<384, decltype(head)>), dim3((M + 3) / 4), dim3(256), 0, st, w.R2, n->g2, n->b2, n->lw, n->lb,
+                     head, xt, M, dt, ctr_inc);
   FL_LAUNCH_CHECK();
   return kOk;
 }
@@ -669,10 +629,14 @@ static int pva_flow_impl(DurNet* nd, DurNet* ns, const float* enc, const uint8_t
     if ((rc = pva_persist_run(nd, ns, w, mask, dur_t, sil_t, nfe, B, L, dt, st, &done, dl))) return rc;
     if (done) return kOk;
   }
+  auto step = [&](DurNet* n, const float* P, const float* temb, float* xt, const NetBufs& nb, hipStream_t s, int* ctr, bool split) {
+    return dl ? net_step(n, P, temb, xt, mask, B, L, dt, nb, s, ctr, ctr, split, SeqEnd<true>{dl, 1})
+              : net_step(n, P, temb, xt, mask, B, L, dt, nb, s, ctr, ctr, split, SeqEnd<false>{});
+  };
   if (!(use_graph & 1)) {
     for (int i = 0; i < nfe; ++i) {  // dur then sil on every step (pva.py:104-109)
-      if ((rc = net_step(nd, w.Pd, w.TEMBd + (size_t)i * D, dur_t, mask, B, L, dt, bd, st, nullptr, nullptr, true, dl))) return rc;
-      if ((rc = net_step(ns, w.Ps, w.TEMBs + (size_t)i * D, sil_t, mask, B, L, dt, bs, st, nullptr, nullptr, true, dl))) return rc;
+      if ((rc = step(nd, w.Pd, w.TEMBd + (size_t)i * D, dur_t, bd, st, nullptr, true))) return rc;
+      if ((rc = step(ns, w.Ps, w.TEMBs + (size_t)i * D, sil_t, bs, st, nullptr, true))) return rc;
     }
     return kOk;
   }
@@ -694,28 +658,23 @@ static int pva_flow_impl(DurNet* nd, DurNet* ns, const float* enc, const uint8_t
     if (!gp.cap2) FL_HIP(hipStreamCreateWithFlags(&gp.cap2, hipStreamNonBlocking));
     if (!gp.fork) FL_HIP(hipEventCreateWithFlags(&gp.fork, hipEventDisableTiming));
     if (!gp.join) FL_HIP(hipEventCreateWithFlags(&gp.join, hipEventDisableTiming));
-    FL_HIP(hipStreamBeginCapture(gp.cap, hipStreamCaptureModeRelaxed));
-    int r = kOk;
-    hipError_t fe = hipEventRecord(gp.fork, gp.cap);
-    if (fe == hipSuccess) fe = hipStreamWaitEvent(gp.cap2, gp.fork, 0);
-    if (fe != hipSuccess) r = kHip;
-    // one handle for both nets: its split-K counters would be shared by the concurrent branches
-    const bool split = nd != ns;
-    for (int i = 0; i < G && r == kOk; ++i) r = net_step(nd, w.Pd, w.TEMBd, dur_t, mask, B, L, dt, bd, gp.cap, gp.ctr, gp.ctr, split, dl);
-    for (int i = 0; i < G && r == kOk; ++i)
-      r = net_step(ns, w.Ps, w.TEMBs, sil_t, mask, B, L, dt, bs, gp.cap2, gp.ctr + 1, gp.ctr + 1, split, dl);
-    if (r == kOk) {
-      fe = hipEventRecord(gp.join, gp.cap2);
-      if (fe == hipSuccess) fe = hipStreamWaitEvent(gp.cap, gp.join, 0);
+    rc = capture_exec(gp.cap, &gp.exec, [&](hipStream_t cap) -> int {
+      int r = kOk;
+      hipError_t fe = hipEventRecord(gp.fork, cap);
+      if (fe == hipSuccess) fe = hipStreamWaitEvent(gp.cap2, gp.fork, 0);
       if (fe != hipSuccess) r = kHip;
-    }
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(gp.cap, &g);
-    if (r) { if (g) (void)hipGraphDestroy(g); return r; }
-    FL_HIP(e);
-    hipError_t ie = hipGraphInstantiate(&gp.exec, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    FL_HIP(ie);
+      // one handle for both nets: its split-K counters would be shared by the concurrent branches
+      const bool split = nd != ns;
+      for (int i = 0; i < G && r == kOk; ++i) r = step(nd, w.Pd, w.TEMBd, dur_t, bd, cap, gp.ctr, split);
+      for (int i = 0; i < G && r == kOk; ++i) r = step(ns, w.Ps, w.TEMBs, sil_t, bs, gp.cap2, gp.ctr + 1, split);
+      if (r == kOk) {
+        fe = hipEventRecord(gp.join, gp.cap2);
+        if (fe == hipSuccess) fe = hipStreamWaitEvent(cap, gp.join, 0);
+        if (fe != hipSuccess) r = kHip;
+      }
+      return r;
+    });
+    if (rc) return rc;
     gp.key = key;
   }
   FL_HIP(hipMemsetAsync(gp.ctr, 0, 2 * sizeof(int), st));

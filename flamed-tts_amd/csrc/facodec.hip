@@ -11,6 +11,8 @@
 // LDS-tiled stencil kernel: fp32 in, GEMM-operand dtype out.
 #include "flamed_hip.h"
 #include "gemm.hpp"
+#include "graph.hpp"
+#include "lens.hpp"
 
 #include <vector>
 
@@ -65,21 +67,15 @@ constexpr int kActA = 64;  // output samples per workgroup
 
 // Exact lengths (flamed_fac_decode_lens): utterance b of the padded batch holds lens[b] frames, so at a stage that has
 // upsampled by `mul` its rows are [0, lens[b] * mul) of its n.  Every kernel below decides its edges (replicate clamp,
-// zero pad, last row written) from that end `ne`; the batch stride stays n, and the rows from ne on are neither read
-// nor written (the wav samples there are written as 0).  The dense kernels pass ne = n.
-struct FacLens {
-  const int* __restrict__ lens;  // B device ints, 1 <= lens[b] <= T (handle-owned, filled stream-ordered per call)
-  int mul;
-  __device__ int end(int b) const { return lens[b] * mul; }
-};
+// zero pad, last row written) from that end `ne` = end.end(b, n) (lens.hpp: SeqEnd); the batch stride stays n, and the
+// rows from ne on are neither read nor written (the wav samples there are written as 0).  Dense: ne = n.
 
-// kActCG channels per workgroup (64, or 32 for the encoder's first stage); n = batch stride in rows, ne = this
-// utterance's own end (ne <= n; a0 < ne)
-template <typename OT, int kActCG>
-__device__ __forceinline__ void act1d_body(const float* __restrict__ x, int C, int n, int ne,
-                                           const float* __restrict__ alpha, const float* __restrict__ beta,
-                                           const float* __restrict__ fu, const float* __restrict__ fd,
-                                           OT* __restrict__ out) {
+// kActCG channels per workgroup (64, or 32 for the encoder's first stage); n = batch stride in rows
+template <typename OT, int kActCG, class End = SeqEnd<false>>
+__global__ __launch_bounds__(256) void act1d_kernel(const float* __restrict__ x, int C, int n,
+                                                    const float* __restrict__ alpha, const float* __restrict__ beta,
+                                                    const float* __restrict__ fu, const float* __restrict__ fd,
+                                                    OT* __restrict__ out, End end) {
   constexpr int XR = kActA + 13;      // x rows a0-6 .. a0+A+6
   constexpr int SR = 2 * kActA + 12;  // snake samples j = 2a0-5 .. 2a0+2A+6
   constexpr int RGS = 256 / kActCG;   // row groups
@@ -88,6 +84,10 @@ __device__ __forceinline__ void act1d_body(const float* __restrict__ x, int C, i
   __shared__ float filt[24];
   const int tid = threadIdx.x;
   const int c0 = blockIdx.x * kActCG, a0 = blockIdx.y * kActA, b = blockIdx.z;
+  const int ne = end.end(b, n);
+  if constexpr (End::kExact) {
+    if (a0 >= ne) return;  // a tile that starts at or past its utterance's end has nothing to do (blockIdx-uniform)
+  }
   if (tid < 12) filt[tid] = fu[tid];
   else if (tid < 24) filt[tid] = fd[tid - 12];
   const float* xb = x + (size_t)b * n * C;
@@ -131,32 +131,18 @@ __device__ __forceinline__ void act1d_body(const float* __restrict__ x, int C, i
   }
 }
 
-template <typename OT, int kActCG>
-__global__ __launch_bounds__(256) void act1d_kernel(const float* __restrict__ x, int C, int n,
-                                                    const float* __restrict__ alpha, const float* __restrict__ beta,
-                                                    const float* __restrict__ fu, const float* __restrict__ fd,
-                                                    OT* __restrict__ out) {
-  act1d_body<OT, kActCG>(x, C, n, n, alpha, beta, fu, fd, out);
-}
-
-// exact lengths: a workgroup whose tile starts at or past its utterance's end has nothing to do (blockIdx-uniform)
-template <typename OT, int kActCG>
-__global__ __launch_bounds__(256) void act1d_lens_kernel(const float* __restrict__ x, int C, int n, FacLens fl,
-                                                         const float* __restrict__ alpha, const float* __restrict__ beta,
-                                                         const float* __restrict__ fu, const float* __restrict__ fd,
-                                                         OT* __restrict__ out) {
-  const int ne = fl.end(blockIdx.z);
-  if ((int)blockIdx.y * kActA >= ne) return;
-  act1d_body<OT, kActCG>(x, C, n, ne, alpha, beta, fu, fd, out);
-}
-
 // ------------------------------ prep: LayerNorm over C + timbre affine + transpose ------------------------------
 // lat (B, C, T) channels-first -> h0 (B*T, C): LN(eps 1e-5, no affine) then x*gamma + beta (facodec.py:631-636)
 // Te = this utterance's own frame count (T in the dense call): frames from Te on are neither loaded nor normalised
-__device__ __forceinline__ void fac_prep_body(const float* __restrict__ lat, const float* __restrict__ style, int C, int T,
-                                              int Te, float* __restrict__ h0) {
+template <class End = SeqEnd<false>>
+__global__ __launch_bounds__(256) void fac_prep_kernel(const float* __restrict__ lat, const float* __restrict__ style,
+                                                       int C, int T, float* __restrict__ h0, End end) {
   extern __shared__ float tile[];  // C x 33
   const int b = blockIdx.y, t0 = blockIdx.x * 32, tid = threadIdx.x;
+  const int Te = end.end(b, T);
+  if constexpr (End::kExact) {
+    if (t0 >= Te) return;  // blockIdx-uniform
+  }
   for (int idx = tid; idx < C * 32; idx += 256) {
     int c = idx >> 5, t = idx & 31;
     tile[c * 33 + t] = (t0 + t < Te) ? lat[((size_t)b * C + c) * T + t0 + t] : 0.f;
@@ -187,28 +173,24 @@ __device__ __forceinline__ void fac_prep_body(const float* __restrict__ lat, con
   }
 }
 
-__global__ __launch_bounds__(256) void fac_prep_kernel(const float* __restrict__ lat, const float* __restrict__ style,
-                                                       int C, int T, float* __restrict__ h0) {
-  fac_prep_body(lat, style, C, T, T, h0);
-}
-
-__global__ __launch_bounds__(256) void fac_prep_lens_kernel(const float* __restrict__ lat, const float* __restrict__ style,
-                                                            int C, int T, FacLens fl, float* __restrict__ h0) {
-  const int Te = fl.end(blockIdx.y);
-  if ((int)blockIdx.x * 32 >= Te) return;
-  fac_prep_body(lat, style, C, T, Te, h0);
-}
-
 // ------------------------------ final Conv1d(64 -> 1, k7, pad 3) + tanh ------------------------------
 // ne = this utterance's own end (n in the dense call): taps from ne on are zero, samples ne .. n - 1 are written as 0
-template <typename IT>
-__device__ __forceinline__ void fac_out_body(const IT* __restrict__ act, int C, int n, int ne, const float* __restrict__ w,
-                                             const float* __restrict__ bias, float* __restrict__ wav) {
+template <typename IT, class End = SeqEnd<false>>
+__global__ __launch_bounds__(128) void fac_out_kernel(const IT* __restrict__ act, int C, int n, const float* __restrict__ w,
+                                                      const float* __restrict__ bias, float* __restrict__ wav, End end) {
   constexpr int TS = 128, HALO = 3;
   extern __shared__ float sm[];
   float* rows = sm;                      // (TS + 6) x (C + 1)
   float* ws = sm + (TS + 2 * HALO) * (C + 1);  // C x 7
   const int b = blockIdx.y, t0 = blockIdx.x * TS, tid = threadIdx.x;
+  const int ne = end.end(b, n);
+  if constexpr (End::kExact) {
+    // the wav buffer is reused between calls, so a tile past the utterance's end writes its zeros (blockIdx-uniform)
+    if (t0 >= ne) {
+      if (t0 + tid < n) wav[(size_t)b * n + t0 + tid] = 0.f;
+      return;
+    }
+  }
   for (int i = tid; i < C * 7; i += TS) ws[i] = w[i];
   const IT* ab = act + (size_t)b * n * C;
   for (int idx = tid; idx < (TS + 2 * HALO) * C; idx += TS) {
@@ -230,142 +212,35 @@ __device__ __forceinline__ void fac_out_body(const IT* __restrict__ act, int C, 
   wav[(size_t)b * n + t] = tanhf(acc);
 }
 
-template <typename IT>
-__global__ __launch_bounds__(128) void fac_out_kernel(const IT* __restrict__ act, int C, int n, const float* __restrict__ w,
-                                                      const float* __restrict__ bias, float* __restrict__ wav) {
-  fac_out_body<IT>(act, C, n, n, w, bias, wav);
-}
-
-// exact lengths: the wav buffer is reused between calls, so a tile past the utterance's end writes its zeros
-template <typename IT>
-__global__ __launch_bounds__(128) void fac_out_lens_kernel(const IT* __restrict__ act, int C, int n, FacLens fl,
-                                                           const float* __restrict__ w, const float* __restrict__ bias,
-                                                           float* __restrict__ wav) {
-  const int ne = fl.end(blockIdx.y);
-  const int t = blockIdx.x * 128 + threadIdx.x;
-  if ((int)blockIdx.x * 128 >= ne) {  // blockIdx-uniform
-    if (t < n) wav[(size_t)blockIdx.y * n + t] = 0.f;
-    return;
-  }
-  fac_out_body<IT>(act, C, n, ne, w, bias, wav);
-}
-
 // ------------------------------ GEMM loaders / epilogues ------------------------------
 
-// ConvTranspose phase GEMM A operand: row m -> (b, q), q in [0, n]; tap 0 = x[q], tap 1 = x[q-1].
-template <typename DT>
+// ConvTranspose phase GEMM A operand: row m -> (b, q), q in [0, n]; tap 0 = x[q], tap 1 = x[q-1].  A tap is zero when
+// its source row is outside [0, ne) of its utterance: q in [0, ne] has sources, tap 1 of q = ne reads x[ne - 1].
+template <typename DT, class End = SeqEnd<false>>
 struct LoadConvT {
   const DT* __restrict__ x;
   int Cin;
   int n;
+  [[no_unique_address]] End end;
   struct Raw { u32x4 v; };
   static constexpr int stat_rows(int) { return 0; }
   __device__ void prologue(int, int, int, float*) const {}
   __device__ Raw issue(int m, int k) const {
-    int b = m / (n + 1), q = m - b * (n + 1);
+    const int b = m / (n + 1), q = m - b * (n + 1), ne = end.end(b, n);  // (read ahead of the test, not behind i < 0)
     int tap = k / Cin, c = k - tap * Cin;
     int i = q - tap;
-    if (i < 0 || i >= n) return Raw{u32x4{0u, 0u, 0u, 0u}};
-    return Raw{*reinterpret_cast<const u32x4*>(x + ((size_t)b * n + i) * Cin + c)};
-  }
-  template <typename D> __device__ u32x4 finish(const Raw& r, int, int, const float*, int) const { return r.v; }
-};
-
-struct EpiConvTStore {
-  const float* __restrict__ bias;
-  float* __restrict__ out;
-  int Cout, n, s, r, p;
-  static constexpr bool kRowStats = false;
-  static constexpr int stat_rows(int) { return 0; }
-  __device__ void prologue(int, int, int, float*) const {}
-  __device__ float value(int, int col, float acc, const float*, int) const { return acc + bias[col]; }
-  __device__ void store(int m, int col, float v) const {
-    int b = m / (n + 1), q = m - b * (n + 1);
-    int o = q * s + r - p;
-    if (o >= 0 && o < s * n) out[((size_t)b * s * n + o) * Cout + col] = v;
-  }
-  __device__ void store_stats(int, int, float, float) const {}
-};
-
-// ---- exact-lengths forms: a tap is zero when its source row is outside [0, ne) of its utterance; a row at or past
-// ne loads nothing (its result is never read by a valid row: a GEMM row depends on its own A row only).
-
-// conv_in: Conv1d(k = KT, pad KT/2) over the fp32 styled-LayerNorm rows h0 (B*T, Cin), packed to DT
-template <typename DT>
-struct LoadConvInLens {
-  const float* __restrict__ x;
-  int Cin, L, KT;
-  FacLens fl;
-  static constexpr int EPC = DTraits<DT>::EPC;
-  struct Raw { float v[EPC]; };
-  static constexpr int stat_rows(int) { return 0; }
-  __device__ void prologue(int, int, int, float*) const {}
-  __device__ Raw issue(int m, int k) const {
-    Raw r;
-    const int b = m / L, l = m - b * L, ne = fl.end(b);
-    const int tap = k / Cin, c = k - tap * Cin;
-    const int off = tap - KT / 2;
-    const int i = l + off;
-    if (l < ne && i >= 0 && i < ne) {
-      const float* px = x + (size_t)(m + off) * Cin + c;
-#pragma unroll
-      for (int j = 0; j < EPC; j += 4) {
-        float4 a = ld4(px + j);
-        r.v[j] = a.x; r.v[j + 1] = a.y; r.v[j + 2] = a.z; r.v[j + 3] = a.w;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < EPC; ++j) r.v[j] = 0.f;
-    }
-    return r;
-  }
-  template <typename D> __device__ u32x4 finish(const Raw& r, int, int, const float*, int) const { return pack_chunk<D>(r.v); }
-};
-
-// dilated k7 conv of a residual unit over the DT activation (B*L, Cin)
-template <typename DT>
-struct LoadConvPlainLens {
-  const DT* __restrict__ x;
-  int Cin, L, KT, dil;
-  FacLens fl;
-  struct Raw { u32x4 v; };
-  static constexpr int stat_rows(int) { return 0; }
-  __device__ void prologue(int, int, int, float*) const {}
-  __device__ Raw issue(int m, int k) const {
-    const int b = m / L, l = m - b * L, ne = fl.end(b);
-    const int tap = k / Cin, c = k - tap * Cin;
-    const int off = (tap - KT / 2) * dil;
-    const int i = l + off;
-    if (l >= ne || i < 0 || i >= ne) return Raw{u32x4{0u, 0u, 0u, 0u}};
-    return Raw{*reinterpret_cast<const u32x4*>(x + (size_t)(m + off) * Cin + c)};
-  }
-  template <typename D> __device__ u32x4 finish(const Raw& r, int, int, const float*, int) const { return r.v; }
-};
-
-// LoadConvT with the utterance's own end: q in [0, ne] has sources, tap 1 of q = ne reads x[ne - 1]
-template <typename DT>
-struct LoadConvTLens {
-  const DT* __restrict__ x;
-  int Cin, n;
-  FacLens fl;
-  struct Raw { u32x4 v; };
-  static constexpr int stat_rows(int) { return 0; }
-  __device__ void prologue(int, int, int, float*) const {}
-  __device__ Raw issue(int m, int k) const {
-    const int b = m / (n + 1), q = m - b * (n + 1), ne = fl.end(b);
-    const int tap = k / Cin, c = k - tap * Cin;
-    const int i = q - tap;
     if (i < 0 || i >= ne) return Raw{u32x4{0u, 0u, 0u, 0u}};
     return Raw{*reinterpret_cast<const u32x4*>(x + ((size_t)b * n + i) * Cin + c)};
   }
   template <typename D> __device__ u32x4 finish(const Raw& r, int, int, const float*, int) const { return r.v; }
 };
 
-struct EpiConvTStoreLens {  // EpiConvTStore that stores o < s * ne only
+template <class End = SeqEnd<false>>
+struct EpiConvTStore {  // stores o < s * ne only
   const float* __restrict__ bias;
   float* __restrict__ out;
   int Cout, n, s, r, p;
-  FacLens fl;
+  [[no_unique_address]] End end;
   static constexpr bool kRowStats = false;
   static constexpr int stat_rows(int) { return 0; }
   __device__ void prologue(int, int, int, float*) const {}
@@ -373,7 +248,7 @@ struct EpiConvTStoreLens {  // EpiConvTStore that stores o < s * ne only
   __device__ void store(int m, int col, float v) const {
     int b = m / (n + 1), q = m - b * (n + 1);
     int o = q * s + r - p;
-    if (o >= 0 && o < s * fl.end(b)) out[((size_t)b * s * n + o) * Cout + col] = v;
+    if (o >= 0 && o < s * end.end(b, n)) out[((size_t)b * s * n + o) * Cout + col] = v;
   }
   __device__ void store_stats(int, int, float, float) const {}
 };
@@ -412,25 +287,16 @@ struct Fac {
   char* dev = nullptr;
   int device = -1;  // device of the arena (from the loaded weights)
   std::mutex mu;    // one call at a time per handle
-  hipGraphExec_t gexec = nullptr;
-  hipStream_t cap = nullptr;
-  std::vector<const void*> gkey;
   // exact lengths: a graph of its own (the dense and the ragged call of one (B, T) never replay each other's) whose
   // kernels read this call's lengths from dlens, filled stream-ordered ahead of the replay
-  hipGraphExec_t gexec_l = nullptr;
-  std::vector<const void*> gkey_l;
-  int* dlens = nullptr;
-  int dlens_cap = 0;
+  CapGraph graph, graph_l;
+  DevLens dlens;
   void release() {
-    retire_graph(gexec);
-    retire_graph(gexec_l);
-    if (cap) (void)hipStreamDestroy(cap);
+    graph.release();
+    graph_l.release();
+    dlens.release();
     if (dev) (void)hipFree(dev);
-    if (dlens) (void)hipFree(dlens);
-    gexec = nullptr; gexec_l = nullptr; cap = nullptr; dev = nullptr; dlens = nullptr;
-    dlens_cap = 0;
-    gkey.clear();
-    gkey_l.clear();
+    dev = nullptr;
   }
 };
 
@@ -458,124 +324,62 @@ static size_t fac_ws_layout(const Fac* f, int B, int T, void* base, FacWs* w) {
   return off;
 }
 
-template <typename DT>
-static int launch_act(const FacAct& a, const float* x, int C, int n, int B, DT* out, hipStream_t st) {
+template <typename DT, class End = SeqEnd<false>>
+static int launch_act(const FacAct& a, const float* x, int C, int n, int B, DT* out, hipStream_t st, End end = {}) {
   FL_REQUIRE(C % 32 == 0, "act1d: C=%d must be a multiple of 32", C);
   const int na = (n + kActA - 1) / kActA;
   if (C % 64 == 0)
-    hipLaunchKernelGGL((act1d_kernel<DT, 64>), dim3(C / 64, na, B), dim3(256), 0, st, x, C, n, a.alpha, a.beta, a.fu, a.fd, out);
+    hipLaunchKernelGGL((act1d_kernel<DT, 64, End>), dim3(C / 64, na, B), dim3(256), 0, st, x, C, n, a.alpha, a.beta, a.fu, a.fd, out, end);
   else
-    hipLaunchKernelGGL((act1d_kernel<DT, 32>), dim3(C / 32, na, B), dim3(256), 0, st, x, C, n, a.alpha, a.beta, a.fu, a.fd, out);
+    hipLaunchKernelGGL((act1d_kernel<DT, 32, End>), dim3(C / 32, na, B), dim3(256), 0, st, x, C, n, a.alpha, a.beta, a.fu, a.fd, out, end);
   FL_LAUNCH_CHECK();
   return kOk;
 }
 
-template <typename DT>
-static int launch_act_lens(const FacAct& a, const float* x, int C, int n, int B, FacLens fl, DT* out, hipStream_t st) {
-  FL_REQUIRE(C % 64 == 0, "act1d: C=%d must be a multiple of 64", C);
-  const int na = (n + kActA - 1) / kActA;
-  hipLaunchKernelGGL((act1d_lens_kernel<DT, 64>), dim3(C / 64, na, B), dim3(256), 0, st, x, C, n, fl, a.alpha, a.beta, a.fu, a.fd, out);
-  FL_LAUNCH_CHECK();
-  return kOk;
-}
-
-// This call's lengths travel as a kernel argument (copied at launch, so the caller's array may go at once) and are
-// written to the handle's device array in stream order, ahead of the kernels (or the graph replay) that read them.
-constexpr int kLensChunk = 64;
-struct LensArg { int v[kLensChunk]; };
-__global__ __launch_bounds__(kLensChunk) void fac_set_lens_kernel(LensArg a, int cnt, int* __restrict__ dst) {
-  const int i = threadIdx.x;
-  if (i < cnt) dst[i] = a.v[i];
-}
-
-static int fac_set_lens(Fac* f, const int* lens, int B, hipStream_t st) {
-  if (B > f->dlens_cap) {  // grows only; the pointer is part of the ragged graph's key
-    retire_graph(f->gexec_l);
-    f->gkey_l.clear();
-    if (f->dlens) FL_HIP(hipFree(f->dlens));  // (waits for the work that may still read it)
-    f->dlens = nullptr;
-    f->dlens_cap = 0;
-    const int cap = (B + kLensChunk - 1) / kLensChunk * kLensChunk;
-    FL_HIP(hipMalloc(&f->dlens, sizeof(int) * cap));
-    f->dlens_cap = cap;
-  }
-  for (int b0 = 0; b0 < B; b0 += kLensChunk) {
-    LensArg a;
-    const int cnt = B - b0 < kLensChunk ? B - b0 : kLensChunk;
-    for (int i = 0; i < kLensChunk; ++i) a.v[i] = i < cnt ? lens[b0 + i] : 0;
-    hipLaunchKernelGGL(fac_set_lens_kernel, dim3(1), dim3(kLensChunk), 0, st, a, cnt, f->dlens + b0);
-    FL_LAUNCH_CHECK();
-  }
-  return kOk;
-}
-
-// RAG: the exact-lengths decode -- the same launches with the kernels and loaders that take each utterance's own end
-// from `lens` (B device ints); the dense instantiation (RAG = false) is the decode as it always was.
-template <typename DT, bool RAG = false>
+// RAG: the exact-lengths decode -- the same launches, every kernel and loader taking each utterance's own end from
+// `lens` (B device ints) through its stage's SeqEnd<true>; the dense instantiation (RAG = false) is the decode as it
+// always was.
+template <typename DT, bool RAG>
 static int fac_decode_impl(Fac* f, const float* lat, const float* spk, int B, int T, float* wav, const FacWs& w,
-                           hipStream_t st, const int* lens = nullptr) {
+                           hipStream_t st, const int* lens) {
+  using End = SeqEnd<RAG>;
   int rc;
 #define TRY(x) do { if ((rc = (x)) != kOk) return rc; } while (0)
   const int C0 = f->C0;
   DT* A = reinterpret_cast<DT*>(w.A);
   TRY((launch_gemm<float>(LoadF32<float>{spk, C0}, f->tlw, C0, EpiBiasAct<float, 0>{f->tlb, w.style, 2 * C0}, B, 2 * C0, C0, st)));
-  if constexpr (RAG) {
-    const FacLens fl0{lens, 1};
-    hipLaunchKernelGGL(fac_prep_lens_kernel, dim3((T + 31) / 32, B), dim3(256), (size_t)C0 * 33 * 4, st, lat, w.style, C0, T, fl0,
-                       w.h0);
-    FL_LAUNCH_CHECK();
-    TRY((gemm_auto<DT>(LoadConvInLens<DT>{w.h0, C0, T, 7, FacLens{lens, 1}}, (const DT*)f->win, 7 * C0,
-                       EpiBiasAct<float, 0>{f->bin, w.X, f->CI}, B * T, f->CI, 7 * C0, st)));
-  } else {
-    hipLaunchKernelGGL(fac_prep_kernel, dim3((T + 31) / 32, B), dim3(256), (size_t)C0 * 33 * 4, st, lat, w.style, C0, T, w.h0);
-    FL_LAUNCH_CHECK();
-    TRY((gemm_auto<DT>(LoadConvRows<DT, false>{w.h0, C0, T, 7, 1, nullptr, 0, 0, 0.f, nullptr, nullptr}, (const DT*)f->win, 7 * C0,
-                       EpiBiasAct<float, 0>{f->bin, w.X, f->CI}, B * T, f->CI, 7 * C0, st)));
-  }
-  // Activation1d at a stage whose rows are n = T * mul per utterance
-  auto act = [&](const FacAct& a, const float* x, int C, int n, int mul) -> int {
-    if constexpr (RAG) return launch_act_lens<DT>(a, x, C, n, B, FacLens{lens, mul}, A, st);
-    else return launch_act<DT>(a, x, C, n, B, A, st);
-  };
-  int n = T, mul = 1;
+  int n = T, mul = 1;  // a stage's rows per utterance, and per frame
+  End end = End::make(lens, mul);
+  hipLaunchKernelGGL(fac_prep_kernel<End>, dim3((T + 31) / 32, B), dim3(256), (size_t)C0 * 33 * 4, st, lat, w.style, C0, T, w.h0, end);
+  FL_LAUNCH_CHECK();
+  TRY((gemm_auto<DT>(LoadConvRows<DT, false, End>{w.h0, C0, T, 7, 1, nullptr, 0, 0, 0.f, nullptr, nullptr, end}, (const DT*)f->win,
+                     7 * C0, EpiBiasAct<float, 0>{f->bin, w.X, f->CI}, B * T, f->CI, 7 * C0, st)));
   for (int i = 0; i < f->NUP; ++i) {
     const FacBlk& bk = f->blk[i];
     const int s = bk.s, Cin = bk.cin, Cout = bk.cout, p = s / 2 + s % 2;
-    TRY(act(bk.a, w.X, Cin, n, mul));
+    TRY(launch_act<DT>(bk.a, w.X, Cin, n, B, A, st, end));
     for (int r = 0; r < s; ++r) {
       const DT* Wr = (const DT*)bk.wt + (size_t)r * Cout * 2 * Cin;
-      if constexpr (RAG)
-        TRY((gemm_auto<DT>(LoadConvTLens<DT>{A, Cin, n, FacLens{lens, mul}}, Wr, 2 * Cin,
-                           EpiConvTStoreLens{bk.bt, w.X, Cout, n, s, r, p, FacLens{lens, mul}}, B * (n + 1), Cout, 2 * Cin, st)));
-      else
-        TRY((gemm_auto<DT>(LoadConvT<DT>{A, Cin, n}, Wr, 2 * Cin, EpiConvTStore{bk.bt, w.X, Cout, n, s, r, p}, B * (n + 1), Cout,
-                           2 * Cin, st)));
+      TRY((gemm_auto<DT>(LoadConvT<DT, End>{A, Cin, n, end}, Wr, 2 * Cin, EpiConvTStore<End>{bk.bt, w.X, Cout, n, s, r, p, end},
+                         B * (n + 1), Cout, 2 * Cin, st)));
     }
     n *= s;
     mul *= s;
+    end = End::make(lens, mul);
     for (int j = 0; j < 3; ++j) {
       const FacRU& ru = bk.ru[j];
-      TRY(act(ru.a1, w.X, Cout, n, mul));
-      if constexpr (RAG)
-        TRY((gemm_auto<DT>(LoadConvPlainLens<DT>{A, Cout, n, 7, ru.dil, FacLens{lens, mul}}, (const DT*)ru.w7, 7 * Cout,
-                           EpiBiasAct<float, 0>{ru.b7, w.Z, Cout}, B * n, Cout, 7 * Cout, st)));
-      else
-        TRY((gemm_auto<DT>(LoadConvPlain<DT>{A, Cout, n, 7, ru.dil}, (const DT*)ru.w7, 7 * Cout,
-                           EpiBiasAct<float, 0>{ru.b7, w.Z, Cout}, B * n, Cout, 7 * Cout, st)));
-      TRY(act(ru.a2, w.Z, Cout, n, mul));
+      TRY(launch_act<DT>(ru.a1, w.X, Cout, n, B, A, st, end));
+      TRY((gemm_auto<DT>(LoadConvPlain<DT, End>{A, Cout, n, 7, ru.dil, end}, (const DT*)ru.w7, 7 * Cout,
+                         EpiBiasAct<float, 0>{ru.b7, w.Z, Cout}, B * n, Cout, 7 * Cout, st)));
+      TRY(launch_act<DT>(ru.a2, w.Z, Cout, n, B, A, st, end));
       // the 1x1 conv has no edge: a row reads its own row only (rows past an utterance's end hold anything)
       TRY((gemm_auto<DT>(LoadPlain<DT>{A, Cout}, (const DT*)ru.w1, Cout, EpiResAdd{ru.b1, w.X, Cout}, B * n, Cout, Cout, st)));
     }
   }
   const int cf = f->cfin;
-  TRY(act(f->afin, w.X, cf, n, mul));
+  TRY(launch_act<DT>(f->afin, w.X, cf, n, B, A, st, end));
   size_t smem = ((128 + 6) * (cf + 1) + cf * 7) * 4;
-  if constexpr (RAG) {
-    const FacLens flo{lens, mul};
-    hipLaunchKernelGGL(fac_out_lens_kernel<DT>, dim3((n + 127) / 128, B), dim3(128), smem, st, A, cf, n, flo, f->wout, f->bout, wav);
-  } else {
-    hipLaunchKernelGGL(fac_out_kernel<DT>, dim3((n + 127) / 128, B), dim3(128), smem, st, A, cf, n, f->wout, f->bout, wav);
-  }
+  hipLaunchKernelGGL((fac_out_kernel<DT, End>), dim3((n + 127) / 128, B), dim3(128), smem, st, A, cf, n, f->wout, f->bout, wav, end);
   FL_LAUNCH_CHECK();
 #undef TRY
   return kOk;
@@ -723,8 +527,8 @@ FLAMED_API int flamed_fac_load(flamed_fac_t h, const float* const* w, int nw, hi
     }
   }
   FL_HIP(hipStreamSynchronize(st));  // the fold scratch is reused per conv on the same stream; drain before returning
-  retire_graph(f->gexec);
-  retire_graph(f->gexec_l);
+  f->graph.retire();
+  f->graph_l.retire();
   return kOk;
 }
 
@@ -733,45 +537,47 @@ FLAMED_API size_t flamed_fac_workspace_size(flamed_fac_t h, int B, int T) {
   return f ? fac_ws_layout(f, B, T, nullptr, nullptr) : 0;
 }
 
+// The decode behind flamed_fac_decode (hlens null) and flamed_fac_decode_lens (hlens: B host lengths, already checked,
+// not all T).  `who` names the entry point in error messages.
+static int fac_decode_call(Fac* f, const char* who, const float* latents, const float* spk, int B, int T, const int* hlens,
+                           float* wav, void* ws, size_t ws_bytes, int use_graph, hipStream_t st) {
+  std::lock_guard<std::mutex> lk(f->mu);
+  FL_ON_DEVICE(f->device);
+  FL_REQUIRE_ON(latents, f->device, who);
+  const Tune tsnap = tune_snapshot(nullptr);
+  TuneScope ts_(&tsnap);
+  if (ws_bytes < fac_ws_layout(f, B, T, nullptr, nullptr)) {
+    set_error("%s: workspace too small", who);
+    return kNoWorkspace;
+  }
+  FacWs w;
+  fac_ws_layout(f, B, T, ws, &w);
+  std::vector<const void*> key = {latents, spk, wav, ws, (const void*)(intptr_t)B, (const void*)(intptr_t)T, f->dev};
+  const int* dl = nullptr;
+  if (hlens) {  // stream-ordered ahead of the kernels / the replay below
+    bool moved = false;
+    const int rc = f->dlens.put(hlens, B, st, &moved);
+    if (rc) return rc;
+    if (moved) f->graph_l.retire();
+    // the graph holds no length: one capture per (pointers, B, T) serves every ragged call of that shape
+    dl = f->dlens.d;
+    key.push_back(dl);
+  }
+  const bool b16 = f->dt == FLAMED_BF16;
+  return with_graph(dl ? f->graph_l : f->graph, key, use_graph != 0, st, [&](hipStream_t s) -> int {
+    if (dl) return b16 ? fac_decode_impl<bf16, true>(f, latents, spk, B, T, wav, w, s, dl)
+                       : fac_decode_impl<float, true>(f, latents, spk, B, T, wav, w, s, dl);
+    return b16 ? fac_decode_impl<bf16, false>(f, latents, spk, B, T, wav, w, s, nullptr)
+               : fac_decode_impl<float, false>(f, latents, spk, B, T, wav, w, s, nullptr);
+  });
+}
+
 FLAMED_API int flamed_fac_decode(flamed_fac_t h, const float* latents, const float* spk, int B, int T, float* wav,
                                  void* ws, size_t ws_bytes, int use_graph, hipStream_t st) {
   Fac* f = reinterpret_cast<Fac*>(h);
   FL_REQUIRE(f && f->dev, "flamed_fac_decode: handle not loaded");
   FL_REQUIRE(latents && spk && wav && ws && B > 0 && T > 0, "flamed_fac_decode: bad args");
-  std::lock_guard<std::mutex> lk(f->mu);
-  FL_ON_DEVICE(f->device);
-  FL_REQUIRE_ON(latents, f->device, "flamed_fac_decode");
-  const Tune tsnap = tune_snapshot(nullptr);
-  TuneScope ts_(&tsnap);
-  if (ws_bytes < fac_ws_layout(f, B, T, nullptr, nullptr)) {
-    set_error("flamed_fac_decode: workspace too small");
-    return kNoWorkspace;
-  }
-  FacWs w;
-  fac_ws_layout(f, B, T, ws, &w);
-  auto run = [&](hipStream_t s) -> int {
-    return f->dt == FLAMED_BF16 ? fac_decode_impl<bf16>(f, latents, spk, B, T, wav, w, s)
-                                : fac_decode_impl<float>(f, latents, spk, B, T, wav, w, s);
-  };
-  if (!use_graph) return run(st);
-  std::vector<const void*> key = {latents, spk, wav, ws, (const void*)(intptr_t)B, (const void*)(intptr_t)T, f->dev};
-  if (!f->gexec || f->gkey != key) {
-    retire_graph(f->gexec);
-    if (!f->cap) FL_HIP(hipStreamCreateWithFlags(&f->cap, hipStreamNonBlocking));
-    FL_HIP(hipStreamBeginCapture(f->cap, hipStreamCaptureModeRelaxed));
-    int r = run(f->cap);
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(f->cap, &g);
-    if (r) { if (g) (void)hipGraphDestroy(g); return r; }
-    FL_HIP(e);
-    hipError_t ie = hipGraphInstantiate(&f->gexec, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    FL_HIP(ie);
-    f->gkey = key;
-  }
-  FL_HIP(hipGraphLaunch(f->gexec, st));
-  note_graph_use(f->gexec, st);
-  return kOk;
+  return fac_decode_call(f, "flamed_fac_decode", latents, spk, B, T, nullptr, wav, ws, ws_bytes, use_graph, st);
 }
 
 FLAMED_API int flamed_fac_decode_lens(flamed_fac_t h, const float* latents, const float* spk, int B, int T, const int* lens,
@@ -787,46 +593,7 @@ FLAMED_API int flamed_fac_decode_lens(flamed_fac_t h, const float* latents, cons
   if (dense) return flamed_fac_decode(h, latents, spk, B, T, wav, ws, ws_bytes, use_graph, st);  // the dense call itself
   Fac* f = reinterpret_cast<Fac*>(h);
   FL_REQUIRE(f->dev, "flamed_fac_decode_lens: handle not loaded");
-  std::lock_guard<std::mutex> lk(f->mu);
-  FL_ON_DEVICE(f->device);
-  FL_REQUIRE_ON(latents, f->device, "flamed_fac_decode_lens");
-  const Tune tsnap = tune_snapshot(nullptr);
-  TuneScope ts_(&tsnap);
-  if (ws_bytes < fac_ws_layout(f, B, T, nullptr, nullptr)) {
-    set_error("flamed_fac_decode_lens: workspace too small");
-    return kNoWorkspace;
-  }
-  FacWs w;
-  fac_ws_layout(f, B, T, ws, &w);
-  {
-    const int rc = fac_set_lens(f, lens, B, st);  // stream-ordered ahead of the kernels / the replay below
-    if (rc) return rc;
-  }
-  const int* dl = f->dlens;
-  auto run = [&](hipStream_t s) -> int {
-    return f->dt == FLAMED_BF16 ? fac_decode_impl<bf16, true>(f, latents, spk, B, T, wav, w, s, dl)
-                                : fac_decode_impl<float, true>(f, latents, spk, B, T, wav, w, s, dl);
-  };
-  if (!use_graph) return run(st);
-  // the graph holds no length: one capture per (pointers, B, T) serves every ragged call of that shape
-  std::vector<const void*> key = {latents, spk, wav, ws, (const void*)(intptr_t)B, (const void*)(intptr_t)T, f->dev, dl};
-  if (!f->gexec_l || f->gkey_l != key) {
-    retire_graph(f->gexec_l);
-    if (!f->cap) FL_HIP(hipStreamCreateWithFlags(&f->cap, hipStreamNonBlocking));
-    FL_HIP(hipStreamBeginCapture(f->cap, hipStreamCaptureModeRelaxed));
-    int r = run(f->cap);
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(f->cap, &g);
-    if (r) { if (g) (void)hipGraphDestroy(g); return r; }
-    FL_HIP(e);
-    hipError_t ie = hipGraphInstantiate(&f->gexec_l, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    FL_HIP(ie);
-    f->gkey_l = key;
-  }
-  FL_HIP(hipGraphLaunch(f->gexec_l, st));
-  note_graph_use(f->gexec_l, st);
-  return kOk;
+  return fac_decode_call(f, "flamed_fac_decode_lens", latents, spk, B, T, lens, wav, ws, ws_bytes, use_graph, st);
 }
 
 }  // extern "C"
@@ -934,15 +701,11 @@ struct Enc {
   char* dev = nullptr;
   int device = -1;  // device of the arena (from the loaded weights)
   std::mutex mu;    // one call at a time per handle
-  hipGraphExec_t gexec = nullptr;
-  hipStream_t cap = nullptr;
-  std::vector<const void*> gkey;
+  CapGraph graph;
   void release() {
-    retire_graph(gexec);
-    if (cap) (void)hipStreamDestroy(cap);
+    graph.release();
     if (dev) (void)hipFree(dev);
-    gexec = nullptr; cap = nullptr; dev = nullptr;
-    gkey.clear();
+    dev = nullptr;
   }
 };
 
@@ -1159,7 +922,7 @@ FLAMED_API int flamed_enc_load(flamed_enc_t h, const float* const* w, int nw, hi
   }
   e->wfin = e->dev + convs[ifin].off;
   FL_HIP(hipStreamSynchronize(st));  // fold scratch reused per conv
-  retire_graph(e->gexec);
+  e->graph.retire();
   return kOk;
 }
 
@@ -1185,28 +948,10 @@ FLAMED_API int flamed_enc_encode(flamed_enc_t h, const float* wav, int B, int n,
   }
   EncWs w;
   enc_ws_layout(e, B, n, ws, &w);
-  auto run = [&](hipStream_t s) -> int {
+  const std::vector<const void*> key = {wav, out, ws, (const void*)(intptr_t)B, (const void*)(intptr_t)n, e->dev};
+  return with_graph(e->graph, key, use_graph != 0, st, [&](hipStream_t s) -> int {
     return e->dt == FLAMED_BF16 ? enc_impl<bf16>(e, wav, B, n, out, w, s) : enc_impl<float>(e, wav, B, n, out, w, s);
-  };
-  if (!use_graph) return run(st);
-  std::vector<const void*> key = {wav, out, ws, (const void*)(intptr_t)B, (const void*)(intptr_t)n, e->dev};
-  if (!e->gexec || e->gkey != key) {
-    retire_graph(e->gexec);
-    if (!e->cap) FL_HIP(hipStreamCreateWithFlags(&e->cap, hipStreamNonBlocking));
-    FL_HIP(hipStreamBeginCapture(e->cap, hipStreamCaptureModeRelaxed));
-    int r = run(e->cap);
-    hipGraph_t g = nullptr;
-    hipError_t er = hipStreamEndCapture(e->cap, &g);
-    if (r) { if (g) (void)hipGraphDestroy(g); return r; }
-    FL_HIP(er);
-    hipError_t ie = hipGraphInstantiate(&e->gexec, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    FL_HIP(ie);
-    e->gkey = key;
-  }
-  FL_HIP(hipGraphLaunch(e->gexec, st));
-  note_graph_use(e->gexec, st);
-  return kOk;
+  });
 }
 
 }  // extern "C"

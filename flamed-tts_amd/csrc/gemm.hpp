@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "seqend.hpp"
 
 namespace fl {
 
@@ -571,8 +572,10 @@ struct EpiBiasStatsT {
 using EpiBiasStats = EpiBiasStatsT<false>;
 
 // Conv1d (kernel KT, pad KT/2, zero padding at each sequence edge) as a GEMM over K = tap*Cin + c,
-// source rows optionally LayerNorm'ed (affine) from producer partials.  Row m = b*L + l.
-template <typename DT, bool LN>
+// source rows optionally LayerNorm'ed (affine) from producer partials.  Row m = b*L + l.  With exact lengths (End =
+// SeqEnd<true>) the window is cut at the row's own utterance's end instead of at L, and a row at or past that end
+// gathers nothing (its result is never read by a valid row: a GEMM row depends on its own A row only).
+template <typename DT, bool LN, class End = SeqEnd<false>>
 struct LoadConvRows {
   const float* __restrict__ x;
   int Cin;
@@ -584,6 +587,7 @@ struct LoadConvRows {
   float eps;
   const float* __restrict__ g;
   const float* __restrict__ bb;
+  [[no_unique_address]] End end;
   static constexpr int EPC = DTraits<DT>::EPC;
   struct Raw { float v[EPC], w[LN ? EPC : 1], b[LN ? EPC : 1]; int src; };
   static constexpr int stat_rows(int BM) { return LN ? BM + 8 : 0; }
@@ -601,8 +605,14 @@ struct LoadConvRows {
     Raw r;
     int tap = k / Cin, c = k - tap * Cin;
     int off = (tap - KT / 2) * dil;
-    int l = m % L + off;
-    r.src = (l >= 0 && l < L) ? m + off : -1;
+    if constexpr (End::kExact) {
+      const int b = m / L, lm = m - b * L, ne = end.end(b, L);
+      const int l = lm + off;
+      r.src = (lm < ne && l >= 0 && l < ne) ? m + off : -1;
+    } else {
+      int l = m % L + off;
+      r.src = (l >= 0 && l < L) ? m + off : -1;
+    }
     if (r.src >= 0) {
       const float* px = x + (size_t)r.src * Cin + c;
 #pragma unroll
@@ -637,22 +647,29 @@ struct LoadConvRows {
   }
 };
 
-// Dilated conv gather over a DT activation (no transform): K index = tap*Cin + c.
-template <typename DT>
+// Dilated conv gather over a DT activation (no transform): K index = tap*Cin + c.  End as in LoadConvRows.
+template <typename DT, class End = SeqEnd<false>>
 struct LoadConvPlain {
   const DT* __restrict__ x;
   int Cin;
   int L;
   int KT;
   int dil;
+  [[no_unique_address]] End end;
   struct Raw { u32x4 v; };
   static constexpr int stat_rows(int) { return 0; }
   __device__ void prologue(int, int, int, float*) const {}
   __device__ Raw issue(int m, int k) const {
     int tap = k / Cin, c = k - tap * Cin;
     int off = (tap - KT / 2) * dil;
-    int l = m % L + off;
-    if (l < 0 || l >= L) return Raw{u32x4{0u, 0u, 0u, 0u}};
+    if constexpr (End::kExact) {
+      const int b = m / L, lm = m - b * L, ne = end.end(b, L);
+      const int l = lm + off;
+      if (lm >= ne || l < 0 || l >= ne) return Raw{u32x4{0u, 0u, 0u, 0u}};
+    } else {
+      int l = m % L + off;
+      if (l < 0 || l >= L) return Raw{u32x4{0u, 0u, 0u, 0u}};
+    }
     return Raw{*reinterpret_cast<const u32x4*>(x + (size_t)(m + off) * Cin + c)};
   }
   template <typename D> __device__ u32x4 finish(const Raw& r, int, int, const float*, int) const { return r.v; }

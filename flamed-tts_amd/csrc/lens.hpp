@@ -1,7 +1,7 @@
-// Per-utterance lengths of an exact-lengths call (PVA flow, prior decode): the caller's host ints travel as kernel
-// arguments (copied at launch, so the caller's array may go at once) into a handle-owned device array, written in
-// stream order ahead of the kernels (or the graph replay) that read it.  A captured graph therefore holds no
-// length, only the array's address.
+// Per-utterance lengths of an exact-lengths call (FaCodec decode, PVA flow, prior decode): the caller's host ints travel
+// as kernel arguments (copied at launch, so the caller's array may go at once) into a handle-owned device array, written
+// in stream order ahead of the kernels (or the graph replay) that read it.  A captured graph therefore holds no length,
+// only the array's address.  (Where a sequence ends on the device: seqend.hpp.)
 #pragma once
 #include "common.hpp"
 
@@ -9,7 +9,7 @@ namespace fl {
 
 constexpr int kLensChunk = 64;
 struct LensChunk { int v[kLensChunk]; };
-static __global__ __launch_bounds__(kLensChunk) void put_lens_kernel(LensChunk a, int cnt, int* __restrict__ dst) {
+static __global__ __launch_bounds__(kLensChunk) void lens_put_kernel(LensChunk a, int cnt, int* __restrict__ dst) {
   const int i = threadIdx.x;
   if (i < cnt) dst[i] = a.v[i];
 }
@@ -38,7 +38,7 @@ struct DevLens {
       LensChunk a;
       const int cnt = B - b0 < kLensChunk ? B - b0 : kLensChunk;
       for (int i = 0; i < kLensChunk; ++i) a.v[i] = i < cnt ? lens[b0 + i] : 0;
-      hipLaunchKernelGGL(put_lens_kernel, dim3(1), dim3(kLensChunk), 0, st, a, cnt, d + b0);
+      hipLaunchKernelGGL(lens_put_kernel, dim3(1), dim3(kLensChunk), 0, st, a, cnt, d + b0);
       FL_LAUNCH_CHECK();
     }
     return kOk;

@@ -2,6 +2,7 @@
 // (prompt.hip): row LayerNorm (+ key-padding mask), LDS-staged fp32 attention, residual GEMM epilogue.
 #pragma once
 #include "gemm.hpp"
+#include "graph.hpp"
 
 #include <cmath>
 #include <vector>
@@ -481,44 +482,6 @@ static int attention(int DK, const float* QKV, const uint8_t* mask, int B, int n
     case 64: return launch_attn<64>(QKV, mask, B, n, D, H, temp, O, st);
     default: FL_REQUIRE(false, "attention: unsupported head width %d", DK);
   }
-}
-
-
-// One cached hipGraph of a whole stack call, re-captured when the call's key (pointers, shapes) changes.
-struct CapGraph {
-  hipGraphExec_t exec = nullptr;
-  hipStream_t cap = nullptr;
-  std::vector<const void*> key;
-  void release() {
-    retire_graph(exec);
-    if (cap) (void)hipStreamDestroy(cap);
-    *this = CapGraph();
-  }
-};
-
-template <class F>
-static int with_graph(CapGraph& g, const std::vector<const void*>& key_in, bool use_graph, hipStream_t st, F&& body) {
-  if (!use_graph) return body(st);
-  // the captured launches bake in the knobs the body read: the process tune epoch is part of the key
-  std::vector<const void*> key = key_in;
-  key.push_back((const void*)(intptr_t)tune_epoch());
-  if (!g.exec || g.key != key) {
-    retire_graph(g.exec);
-    if (!g.cap) FL_HIP(hipStreamCreateWithFlags(&g.cap, hipStreamNonBlocking));
-    FL_HIP(hipStreamBeginCapture(g.cap, hipStreamCaptureModeRelaxed));
-    int r = body(g.cap);
-    hipGraph_t gr = nullptr;
-    hipError_t e = hipStreamEndCapture(g.cap, &gr);
-    if (r) { if (gr) (void)hipGraphDestroy(gr); return r; }
-    FL_HIP(e);
-    hipError_t ie = hipGraphInstantiate(&g.exec, gr, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(gr);
-    FL_HIP(ie);
-    g.key = key;
-  }
-  FL_HIP(hipGraphLaunch(g.exec, st));
-  note_graph_use(g.exec, st);
-  return kOk;
 }
 
 }  // namespace fl
