@@ -610,47 +610,82 @@ FLAMED_API int flamed_fac_decode_lens(flamed_fac_t h, const float* latents, cons
 namespace fl {
 
 // Direct Conv1d(1 -> C, k7, pad 3): X[(b*n + t)*C + c] = bias[c] + sum_k w[c][k] wav[b][t + k - 3]
+// Exact lengths (flamed_enc_encode_lens): the zero pad sits at the utterance's own end ne, and the rows from ne on are
+// not written (no later stage reads them).
+template <class End = SeqEnd<false>>
 __global__ __launch_bounds__(256) void enc_in_kernel(const float* __restrict__ wav, int n, int C, const float* __restrict__ w,
-                                                     const float* __restrict__ bias, float* __restrict__ X, size_t total) {
+                                                     const float* __restrict__ bias, float* __restrict__ X, size_t total,
+                                                     End end) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
   const int c = i % C;
   const size_t bt = i / C;
   const int t = bt % n;
   const float* wb = wav + (bt - t);
+  int ne = n;
+  if constexpr (End::kExact) {
+    ne = end.end((int)(bt / n), n);
+    if (t >= ne) return;
+  }
   float acc = bias[c];
 #pragma unroll
   for (int k = 0; k < 7; ++k) {
     const int src = t + k - 3;
-    if (src >= 0 && src < n) acc += w[c * 7 + k] * wb[src];
+    if (src >= 0 && src < ne) acc += w[c * 7 + k] * wb[src];
   }
   X[i] = acc;
 }
 
-// Dilated conv tap gather over a DT activation with K zero-padded to the GEMM K-step: k >= kreal -> 0.
-template <typename DT>
+// Dilated conv tap gather over a DT activation with K zero-padded to the GEMM K-step: k >= kreal -> 0.  With exact
+// lengths the window is cut at the row's own utterance's end, and a row at or past that end gathers nothing.
+template <bool EX> struct TileSkip {};  // exact lengths only: whether dead row tiles exit (tn().enc_skip)
+template <> struct TileSkip<true> { int on; };
+template <typename DT, class End = SeqEnd<false>>
 struct LoadConvPad {
   const DT* __restrict__ x;
   int Cin, L, KT, dil, kreal;
+  [[no_unique_address]] End end;
+  [[no_unique_address]] TileSkip<End::kExact> skip;
   struct Raw { u32x4 v; };
+  static constexpr bool kTileSkip = End::kExact;
   static constexpr int stat_rows(int) { return 0; }
   __device__ void prologue(int, int, int, float*) const {}
+  // a tile inside one utterance whose first row is at or past that utterance's end: in the early stages a row is a
+  // sample, so a short prompt in a long batch is mostly such tiles
+  __device__ bool tile_dead(int bm, int BM, int M) const {
+    if constexpr (End::kExact) {
+      if (!skip.on) return false;
+      const int last = bm + BM - 1 < M ? bm + BM - 1 : M - 1;
+      const int b = bm / L;
+      return last / L == b && bm - b * L >= end.end(b, L);
+    }
+    return false;
+  }
   __device__ Raw issue(int m, int k) const {
     if (k >= kreal) return Raw{u32x4{0u, 0u, 0u, 0u}};
     int tap = k / Cin, c = k - tap * Cin;
     int off = (tap - KT / 2) * dil;
-    int l = m % L + off;
-    if (l < 0 || l >= L) return Raw{u32x4{0u, 0u, 0u, 0u}};
+    if constexpr (End::kExact) {
+      const int b = m / L, lm = m - b * L, ne = end.end(b, L);
+      const int l = lm + off;
+      if (lm >= ne || l < 0 || l >= ne) return Raw{u32x4{0u, 0u, 0u, 0u}};
+    } else {
+      int l = m % L + off;
+      if (l < 0 || l >= L) return Raw{u32x4{0u, 0u, 0u, 0u}};
+    }
     return Raw{*reinterpret_cast<const u32x4*>(x + (size_t)(m + off) * Cin + c)};
   }
   template <typename D> __device__ u32x4 finish(const Raw& r, int, int, const float*, int) const { return r.v; }
 };
 
-// Strided conv gather: output row m = (b, o), o < nout; tap t reads x[b][o*s + t - p] (zero outside).
-template <typename DT>
+// Strided conv gather: output row m = (b, o), o < nout; tap t reads x[b][o*s + t - p] (zero outside).  `end` is the end
+// of the INPUT stage: with exact lengths a tap at or past the utterance's own input end is zero, which is the zero pad
+// the utterance has alone (the output rows past its own output end are computed from what is left and never read).
+template <typename DT, class End = SeqEnd<false>>
 struct LoadConvStride {
   const DT* __restrict__ x;
   int Cin, nin, nout, s, p;
+  [[no_unique_address]] End end;
   struct Raw { u32x4 v; };
   static constexpr int stat_rows(int) { return 0; }
   __device__ void prologue(int, int, int, float*) const {}
@@ -658,23 +693,29 @@ struct LoadConvStride {
     const int b = m / nout, o = m - b * nout;
     const int tap = k / Cin, c = k - tap * Cin;
     const int i = o * s + tap - p;
-    if (i < 0 || i >= nin) return Raw{u32x4{0u, 0u, 0u, 0u}};
+    if (i < 0 || i >= end.end(b, nin)) return Raw{u32x4{0u, 0u, 0u, 0u}};
     return Raw{*reinterpret_cast<const u32x4*>(x + ((size_t)b * nin + i) * Cin + c)};
   }
   template <typename D> __device__ u32x4 finish(const Raw& r, int, int, const float*, int) const { return r.v; }
 };
 
-// out (B, N, T) channels-first = acc + bias (the encoder's (B, C, T) output layout)
+// out (B, N, T) channels-first = acc + bias (the encoder's (B, C, T) output layout).  With exact lengths the frames
+// from the utterance's own end on are written as 0 (the output buffer is the caller's and is reused).
+template <class End = SeqEnd<false>>
 struct EpiStoreCF {
   const float* __restrict__ bias;
   float* __restrict__ out;
   int N, T;
+  [[no_unique_address]] End end;
   static constexpr bool kRowStats = false;
   static constexpr int stat_rows(int) { return 0; }
   __device__ void prologue(int, int, int, float*) const {}
   __device__ float value(int, int col, float acc, const float*, int) const { return acc + bias[col]; }
   __device__ void store(int m, int col, float v) const {
     const int b = m / T, t = m - b * T;
+    if constexpr (End::kExact) {
+      if (t >= end.end(b, T)) v = 0.f;
+    }
     out[((size_t)b * N + col) * T + t] = v;
   }
   __device__ void store_stats(int, int, float, float) const {}
@@ -701,9 +742,13 @@ struct Enc {
   char* dev = nullptr;
   int device = -1;  // device of the arena (from the loaded weights)
   std::mutex mu;    // one call at a time per handle
-  CapGraph graph;
+  // exact lengths: a graph of its own, as Fac's; its kernels read the (NDN + 1) x B table of stage lengths from dlens
+  CapGraph graph, graph_l;
+  DevLens dlens;
   void release() {
     graph.release();
+    graph_l.release();
+    dlens.release();
     if (dev) (void)hipFree(dev);
     dev = nullptr;
   }
@@ -746,14 +791,33 @@ static size_t enc_ws_layout(const Enc* e, int B, int n, void* base, EncWs* w) {
   return off;
 }
 
-template <typename DT>
-static int enc_impl(Enc* e, const float* wav, int B, int n, float* out, const EncWs& w, hipStream_t st) {
+// The shortest input that leaves a frame: the stride chain walked backwards (a stage of stride s needs
+// (m - 1) s + 2 s - 2 p input rows for m output rows).
+static int enc_min_len(const Enc* e) {
+  int need = 1;
+  for (int i = e->NDN - 1; i >= 0; --i) {
+    const int s = e->ratios[i], p = s / 2 + s % 2, n = (need - 1) * s + 2 * s - 2 * p;
+    need = n > 1 ? n : 1;
+  }
+  return need;
+}
+
+// RAG: the exact-lengths encode -- the same launches, every kernel, loader and the last epilogue taking each
+// utterance's own end at its stage from `tab`: (NDN + 1) x B device ints, row i = the lengths after i strided stages
+// (the stages are not linear in the length, so each has its own row).  RAG = false is the encode as it always was.
+template <typename DT, bool RAG>
+static int enc_impl(Enc* e, const float* wav, int B, int n, float* out, const EncWs& w, hipStream_t st, const int* tab) {
+  using End = SeqEnd<RAG>;
   int rc;
 #define TRY(x) do { if ((rc = (x)) != kOk) return rc; } while (0)
   DT* A = reinterpret_cast<DT*>(w.A);
+  End end = End::make(tab, 1);
+  // the last conv keeps every tile: its epilogue writes the zeros behind each end
+  TileSkip<RAG> skip{};
+  if constexpr (RAG) skip.on = tn().enc_skip;
   {
     const size_t total = (size_t)B * n * e->ngf;
-    hipLaunchKernelGGL(enc_in_kernel, dim3((total + 255) / 256), dim3(256), 0, st, wav, n, e->ngf, e->w_in, e->b_in, w.X, total);
+    hipLaunchKernelGGL(enc_in_kernel<End>, dim3((total + 255) / 256), dim3(256), 0, st, wav, n, e->ngf, e->w_in, e->b_in, w.X, total, end);
     FL_LAUNCH_CHECK();
   }
   int len = n;
@@ -762,23 +826,24 @@ static int enc_impl(Enc* e, const float* wav, int B, int n, float* out, const En
     const int C = bk.cin;
     for (int j = 0; j < 3; ++j) {
       const EncRU& ru = bk.ru[j];
-      TRY(launch_act<DT>(ru.a1, w.X, C, len, B, A, st));
-      TRY((enc_gemm<DT>(LoadConvPad<DT>{A, C, len, 7, ru.dil, 7 * C}, (const DT*)ru.w7, ru.k7, EpiBiasAct<float, 0>{ru.b7, w.Z, C},
+      TRY(launch_act<DT>(ru.a1, w.X, C, len, B, A, st, end));
+      TRY((enc_gemm<DT>(LoadConvPad<DT, End>{A, C, len, 7, ru.dil, 7 * C, end, skip}, (const DT*)ru.w7, ru.k7, EpiBiasAct<float, 0>{ru.b7, w.Z, C},
                         B * len, C, ru.k7, st)));
-      TRY(launch_act<DT>(ru.a2, w.Z, C, len, B, A, st));
-      TRY((enc_gemm<DT>(LoadConvPad<DT>{A, C, len, 1, 1, C}, (const DT*)ru.w1, ru.k1, EpiResAdd{ru.b1, w.X, C}, B * len, C, ru.k1, st)));
+      TRY(launch_act<DT>(ru.a2, w.Z, C, len, B, A, st, end));
+      TRY((enc_gemm<DT>(LoadConvPad<DT, End>{A, C, len, 1, 1, C, end, skip}, (const DT*)ru.w1, ru.k1, EpiResAdd{ru.b1, w.X, C}, B * len, C, ru.k1, st)));
     }
-    TRY(launch_act<DT>(bk.a, w.X, C, len, B, A, st));
+    TRY(launch_act<DT>(bk.a, w.X, C, len, B, A, st, end));
     const int s = bk.s, p = s / 2 + s % 2;
     const int nout = enc_stride_len(len, s);
     FL_REQUIRE(nout > 0, "flamed_enc_encode: input too short for the stride-%d stage", s);
-    TRY((enc_gemm<DT>(LoadConvStride<DT>{A, C, len, nout, s, p}, (const DT*)bk.wc, 2 * s * C, EpiBiasAct<float, 0>{bk.bc, w.X, bk.cout},
+    TRY((enc_gemm<DT>(LoadConvStride<DT, End>{A, C, len, nout, s, p, end}, (const DT*)bk.wc, 2 * s * C, EpiBiasAct<float, 0>{bk.bc, w.X, bk.cout},
                       B * nout, bk.cout, 2 * s * C, st)));
     len = nout;
+    end = End::make(RAG ? tab + (size_t)(i + 1) * B : nullptr, 1);
   }
   const int cf = e->cfin;
-  TRY(launch_act<DT>(e->afin, w.X, cf, len, B, A, st));
-  TRY((enc_gemm<DT>(LoadConvPad<DT>{A, cf, len, 3, 1, 3 * cf}, (const DT*)e->wfin, kpad64(3 * cf), EpiStoreCF{e->bfin, out, e->cout, len},
+  TRY(launch_act<DT>(e->afin, w.X, cf, len, B, A, st, end));
+  TRY((enc_gemm<DT>(LoadConvPad<DT, End>{A, cf, len, 3, 1, 3 * cf, end, {}}, (const DT*)e->wfin, kpad64(3 * cf), EpiStoreCF<End>{e->bfin, out, e->cout, len, end},
                     B * len, e->cout, kpad64(3 * cf), st)));
 #undef TRY
   return kOk;
@@ -923,6 +988,7 @@ FLAMED_API int flamed_enc_load(flamed_enc_t h, const float* const* w, int nw, hi
   e->wfin = e->dev + convs[ifin].off;
   FL_HIP(hipStreamSynchronize(st));  // fold scratch reused per conv
   e->graph.retire();
+  e->graph_l.retire();
   return kOk;
 }
 
@@ -931,27 +997,69 @@ FLAMED_API size_t flamed_enc_workspace_size(flamed_enc_t h, int B, int n) {
   return e ? enc_ws_layout(e, B, n, nullptr, nullptr) : 0;
 }
 
+// The encode behind flamed_enc_encode (hlens null) and flamed_enc_encode_lens (hlens: B host lengths in samples,
+// already checked, not all n).  `who` names the entry point in error messages.
+static int enc_encode_call(Enc* e, const char* who, const float* wav, int B, int n, const int* hlens, float* out, void* ws,
+                           size_t ws_bytes, int use_graph, hipStream_t st) {
+  std::lock_guard<std::mutex> lk(e->mu);
+  FL_ON_DEVICE(e->device);
+  FL_REQUIRE_ON(wav, e->device, who);
+  const Tune tsnap = tune_snapshot(nullptr);
+  TuneScope ts_(&tsnap);
+  if (ws_bytes < enc_ws_layout(e, B, n, nullptr, nullptr)) {
+    set_error("%s: workspace too small", who);
+    return kNoWorkspace;
+  }
+  EncWs w;
+  enc_ws_layout(e, B, n, ws, &w);
+  std::vector<const void*> key = {wav, out, ws, (const void*)(intptr_t)B, (const void*)(intptr_t)n, e->dev};
+  const int* tab = nullptr;
+  if (hlens) {  // the table of stage lengths, stream-ordered ahead of the kernels / the replay below
+    std::vector<int> host((size_t)(e->NDN + 1) * B);
+    for (int u = 0; u < B; ++u) {
+      int len = hlens[u];
+      host[u] = len;
+      for (int i = 0; i < e->NDN; ++i) host[(size_t)(i + 1) * B + u] = len = enc_stride_len(len, e->ratios[i]);
+    }
+    bool moved = false;
+    const int rc = e->dlens.put(host.data(), (int)host.size(), st, &moved);
+    if (rc) return rc;
+    if (moved) e->graph_l.retire();
+    // the graph holds the table's address and no length: one capture serves every ragged call of these pointers, (B, n)
+    tab = e->dlens.d;
+    key.push_back(tab);
+  }
+  const bool b16 = e->dt == FLAMED_BF16;
+  return with_graph(tab ? e->graph_l : e->graph, key, use_graph != 0, st, [&](hipStream_t s) -> int {
+    if (tab) return b16 ? enc_impl<bf16, true>(e, wav, B, n, out, w, s, tab) : enc_impl<float, true>(e, wav, B, n, out, w, s, tab);
+    return b16 ? enc_impl<bf16, false>(e, wav, B, n, out, w, s, nullptr) : enc_impl<float, false>(e, wav, B, n, out, w, s, nullptr);
+  });
+}
+
 FLAMED_API int flamed_enc_encode(flamed_enc_t h, const float* wav, int B, int n, float* out, void* ws, size_t ws_bytes,
                                  int use_graph, hipStream_t st) {
   Enc* e = reinterpret_cast<Enc*>(h);
   FL_REQUIRE(e && e->dev, "flamed_enc_encode: handle not loaded");
   FL_REQUIRE(wav && out && ws && B > 0 && n > 0, "flamed_enc_encode: bad args");
   FL_REQUIRE(enc_len_after(e, n, e->NDN) > 0, "flamed_enc_encode: n=%d too short", n);
-  std::lock_guard<std::mutex> lk(e->mu);
-  FL_ON_DEVICE(e->device);
-  FL_REQUIRE_ON(wav, e->device, "flamed_enc_encode");
-  const Tune tsnap = tune_snapshot(nullptr);
-  TuneScope ts_(&tsnap);
-  if (ws_bytes < enc_ws_layout(e, B, n, nullptr, nullptr)) {
-    set_error("flamed_enc_encode: workspace too small");
-    return kNoWorkspace;
+  return enc_encode_call(e, "flamed_enc_encode", wav, B, n, nullptr, out, ws, ws_bytes, use_graph, st);
+}
+
+FLAMED_API int flamed_enc_encode_lens(flamed_enc_t h, const float* wav, int B, int n, const int* lens, float* out, void* ws,
+                                      size_t ws_bytes, int use_graph, hipStream_t st) {
+  // every check of the arguments comes before any pointer is touched
+  FL_REQUIRE(h && wav && lens && out && ws, "flamed_enc_encode_lens: null handle, wav, lengths, output or workspace");
+  FL_REQUIRE(B > 0 && n > 0, "flamed_enc_encode_lens: bad dims B=%d n=%d", B, n);
+  Enc* e = reinterpret_cast<Enc*>(h);
+  const int min_n = enc_min_len(e);
+  bool dense = true;
+  for (int u = 0; u < B; ++u) {
+    FL_REQUIRE(lens[u] >= min_n && lens[u] <= n, "flamed_enc_encode_lens: utterance %d has length %d (%d..n = %d)", u, lens[u], min_n, n);
+    dense = dense && lens[u] == n;
   }
-  EncWs w;
-  enc_ws_layout(e, B, n, ws, &w);
-  const std::vector<const void*> key = {wav, out, ws, (const void*)(intptr_t)B, (const void*)(intptr_t)n, e->dev};
-  return with_graph(e->graph, key, use_graph != 0, st, [&](hipStream_t s) -> int {
-    return e->dt == FLAMED_BF16 ? enc_impl<bf16>(e, wav, B, n, out, w, s) : enc_impl<float>(e, wav, B, n, out, w, s);
-  });
+  if (dense) return flamed_enc_encode(h, wav, B, n, out, ws, ws_bytes, use_graph, st);  // the dense call itself
+  FL_REQUIRE(e->dev, "flamed_enc_encode_lens: handle not loaded");
+  return enc_encode_call(e, "flamed_enc_encode_lens", wav, B, n, lens, out, ws, ws_bytes, use_graph, st);
 }
 
 }  // extern "C"

@@ -39,6 +39,10 @@ template <class T> struct kpre_of<T, std::void_t<decltype(T::kPre)>> { static co
 // at the store; the others take plain store / store4.
 template <class T, class = void> struct kstorev_of { static constexpr bool value = false; };
 template <class T> struct kstorev_of<T, std::void_t<decltype(T::kStoreV)>> { static constexpr bool value = T::kStoreV; };
+// A loader with kTileSkip answers tile_dead(bm, BM, M): every row of the tile lies behind its utterance's end, so the
+// workgroup exits before any load (exact-lengths encoder; nothing is stored for such a tile).
+template <class T, class = void> struct kskip_of { static constexpr bool value = false; };
+template <class T> struct kskip_of<T, std::void_t<decltype(T::kTileSkip)>> { static constexpr bool value = T::kTileSkip; };
 template <class EP>
 __device__ __forceinline__ void ep_store(const EP& ep, int m, int n, float v, const float* vec, bool use, int bm, int bn) {
   if constexpr (kstorev_of<EP>::value) ep.store_v(m, n, v, vec, use, bm, bn);
@@ -168,6 +172,9 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_kernel(AL al, const DT* __r
   if (sk.strips > 0) xcd_tile(sk.strips, tx, ty);
   const int bn = tx * BN;
   const int bm = ty * BM;
+  if constexpr (kskip_of<AL>::value) {
+    if (sk.n == 1 && al.tile_dead(bm, BM, M)) return;  // blockIdx-uniform, ahead of every load and barrier
+  }
 
   bool a_uv = false, e_uv = false;  // set by the prologue (per-column vectors staged in LDS)
   typename AL::Raw ra0[ACH], ra1[ACH];

@@ -9,9 +9,13 @@
 //     Conv1d(k) -> ReLU -> Linear :54-83), `x + pe[:B]` (the batch index selects the position vector,
 //     :49-51), last LayerNorm, mean over time (facodec.py:530-532).
 // Exact fp32 (codes must match the reference's argmax; f32 MFMA GEMMs are fp32 FMA chains).
+// flamed_vq_encode_lens runs the same launches on a padded ragged batch, every utterance over its own frames and with
+// position vector pe[0], as if alone (run_vq<true>).
 #include "flamed_hip.h"
 #include "flamed_diag.h"
 #include "gemm.hpp"
+#include "lens.hpp"
+#include "seqend.hpp"
 #include "xfmr.hpp"
 
 #include <mutex>
@@ -59,11 +63,18 @@ struct VqParams {
   int nl[4];
 };
 
-// One workgroup (C = 256 threads, thread c = channel c) per frame (b, t); CD = codebook_dim.
-template <int CD>
+// Exact lengths (flamed_vq_encode_lens): utterance b of the padded batch holds lens[b] frames.  The kernels below take
+// that end through SeqEnd (seqend.hpp); the dense instantiation is the code it was.  PadCode is what a frame behind an
+// end gets as its codes (empty in the dense form).
+template <class End> struct PadCode {};
+template <> struct PadCode<SeqEnd<true>> { int64_t v; };
+
+// One workgroup (C = 256 threads, thread c = channel c) per frame (b, t); CD = codebook_dim.  A frame at or past its
+// utterance's end reads nothing and writes pad.v to its codes and 0 to outs / qbuf (the buffers are reused).
+template <int CD, class End = SeqEnd<false>>
 __global__ __launch_bounds__(256) void rvq_kernel(VqParams P, const float* __restrict__ x, int B, int T,
                                                   float* __restrict__ outs, int64_t* __restrict__ codes,
-                                                  float* __restrict__ qbuf) {
+                                                  float* __restrict__ qbuf, End end, PadCode<End> pad) {
   constexpr int C = 256;
   __shared__ float red[4][CD];
   __shared__ float ze_s[CD];
@@ -72,6 +83,18 @@ __global__ __launch_bounds__(256) void rvq_kernel(VqParams P, const float* __res
   const int c = threadIdx.x, lane = c & 63, w = c >> 6;
   const int b = blockIdx.x / T, t = blockIdx.x - b * T;
   const size_t at = ((size_t)b * C + c) * T + t;  // (B, C, T) layouts
+  if constexpr (End::kExact) {
+    if (t >= end.end(b, T)) {  // blockIdx-uniform
+      int nl = 0;
+      for (int g = 0; g < P.G; ++g) {
+        nl += P.nl[g];
+        qbuf[(size_t)g * B * C * T + at] = 0.f;
+      }
+      for (int li = c; li < nl; li += C) codes[((size_t)li * B + b) * T + t] = pad.v;
+      outs[at] = 0.f;
+      return;
+    }
+  }
   const float xv = x[at];
   float gsum[4] = {0.f, 0.f, 0.f, 0.f};  // per-group quantized sums (qbuf)
   int li = 0;
@@ -145,34 +168,54 @@ __global__ __launch_bounds__(256) void rvq_kernel(VqParams P, const float* __res
 }
 
 // Timbre encoder input: x (B, C, T) -> rows (B*T, C) + pe[b] (transformer.py:49-51: pe[:x.size(0)]).
+// Exact lengths: every utterance gets pe[0], the row it gets alone, and the rows from its end on are written as 0 and
+// x is not read there, so every later row of the workspace is a finite function of finite data (a masked key's V row
+// is multiplied by a zero weight: 0 x NaN would be NaN).
+template <class End = SeqEnd<false>>
 __global__ void timbre_in_kernel(const float* __restrict__ x, const float* __restrict__ pe, int B, int C, int T,
-                                 float* __restrict__ X) {
+                                 float* __restrict__ X, End end) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * C * T) return;
   int t = i % T;
   int bc = i / T;
   int c = bc % C, b = bc / C;
-  X[((size_t)b * T + t) * C + c] = x[i] + pe[(size_t)b * C + c];
+  if constexpr (End::kExact) {
+    X[((size_t)b * T + t) * C + c] = t < end.end(b, T) ? x[i] + pe[c] : 0.f;
+  } else {
+    X[((size_t)b * T + t) * C + c] = x[i] + pe[(size_t)b * C + c];
+  }
+}
+
+// The (B, T) key mask of an exact-lengths call (1 = behind the utterance's end) from the device lengths: what ln_mask
+// (which zeroes the masked rows, the FFN conv's zero pad at the utterance's own end) and attention take.
+__global__ void vq_mask_kernel(const int* __restrict__ lens, int B, int T, uint8_t* __restrict__ mask) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * T) return;
+  int b = i / T, t = i - b * T;
+  mask[i] = t >= lens[b];
 }
 
 // mean over time of the last-LayerNorm rows (facodec.py:531-532): spk[b][c] = sum_t Y[b][t][c] / T.  One workgroup
 // per (64 channels, utterance); wave w sums the frames t = w (mod 8) and wave 0 adds the eight partials in wave
 // order.  The sums are held in fp64: one fp32 running sum over T frames drifts by about sqrt(T / 3) roundings, which
 // from a few hundred frames on is several times the error of the reference's pairwise fp32 mean.
+// Exact lengths: the sum and the divisor end at the utterance's own end Te (the same frames in the same waves as alone).
 constexpr int kMeanWaves = 8;
+template <class End = SeqEnd<false>>
 __global__ __launch_bounds__(64 * kMeanWaves) void mean_t_kernel(const float* __restrict__ Y, int T, int C,
-                                                                 float* __restrict__ spk) {
+                                                                 float* __restrict__ spk, End end) {
   __shared__ double part[kMeanWaves][64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + lane, b = blockIdx.y;
+  const int Te = end.end(b, T);
   double s = 0.0;
   if (c < C)
-    for (int t = w; t < T; t += kMeanWaves) s += (double)Y[((size_t)b * T + t) * C + c];
+    for (int t = w; t < Te; t += kMeanWaves) s += (double)Y[((size_t)b * T + t) * C + c];
   part[w][lane] = s;
   __syncthreads();
   if (w != 0 || c >= C) return;
   for (int u = 1; u < kMeanWaves; ++u) s += part[u][lane];
-  spk[(size_t)b * C + c] = (float)(s / (double)T);
+  spk[(size_t)b * C + c] = (float)(s / (double)Te);
 }
 
 __global__ void vq_taps_kernel(const float* __restrict__ src, float* __restrict__ dst, int N, int Cin, int KT) {
@@ -200,7 +243,20 @@ struct PromptVq {
   const float* pe = nullptr;
   std::vector<TimbreLayer> tl;
   const float *lg = nullptr, *lb = nullptr;
-  CapGraph graph;
+  // exact lengths: a graph of its own whose kernels read this call's lengths from dlens and the key mask built from
+  // them (dmask: B*T bytes, handle-owned so that the workspace is the dense call's)
+  CapGraph graph, graph_l;
+  DevLens dlens;
+  uint8_t* dmask = nullptr;
+  size_t mask_cap = 0;
+  void release_graphs() {
+    graph.release();
+    graph_l.release();
+    dlens.release();
+    if (dmask) (void)hipFree(dmask);
+    dmask = nullptr;
+    mask_cap = 0;
+  }
   int n_vq_layers() const { int s = 0; for (int g = 0; g < G; ++g) s += nl[g]; return s; }
 };
 
@@ -222,31 +278,43 @@ static size_t vq_ws_layout(const PromptVq* p, int B, int T, void* base, VqWs* w)
   return off;
 }
 
+// RAG: the exact-lengths form -- the same launches; `lens` (B device ints) ends every utterance through SeqEnd<true>,
+// `mask` is the (B, T) key mask built from it.  RAG = false is the call as it always was (lens, mask null).
+template <bool RAG>
 static int run_vq(PromptVq* p, const float* x, int B, int T, float* outs, int64_t* codes, float* qbuf, float* spk,
-                  const VqWs& w, hipStream_t st) {
-  hipLaunchKernelGGL(rvq_kernel<8>, dim3(B * T), dim3(256), 0, st, p->vp, x, B, T, outs, codes, qbuf);
+                  const VqWs& w, hipStream_t st, const int* lens, uint8_t* mask, int64_t pad_code) {
+  using End = SeqEnd<RAG>;
+  const End end = End::make(lens, 1);
+  PadCode<End> pad{};
+  if constexpr (RAG) pad.v = pad_code;
+  hipLaunchKernelGGL((rvq_kernel<8, End>), dim3(B * T), dim3(256), 0, st, p->vp, x, B, T, outs, codes, qbuf, end, pad);
   FL_LAUNCH_CHECK();
   const int M = B * T, d = p->d, F = p->F;
-  hipLaunchKernelGGL(timbre_in_kernel, dim3((B * d * T + 255) / 256), dim3(256), 0, st, x, p->pe, B, d, T, w.X);
+  hipLaunchKernelGGL(timbre_in_kernel<End>, dim3((B * d * T + 255) / 256), dim3(256), 0, st, x, p->pe, B, d, T, w.X, end);
   FL_LAUNCH_CHECK();
+  if constexpr (RAG) {
+    hipLaunchKernelGGL(vq_mask_kernel, dim3((M + 255) / 256), dim3(256), 0, st, lens, B, T, mask);
+    FL_LAUNCH_CHECK();
+  }
   float* X = w.X;
   float* R = w.R;
   int rc;
   for (const TimbreLayer& L : p->tl) {  // pre-LN layer, transformer.py:122-151
-    if ((rc = ln_mask(d, X, L.g1, L.b1, nullptr, w.H, M, T, nullptr, 0, 0, 0, 0, st))) return rc;
+    if ((rc = ln_mask(d, X, L.g1, L.b1, mask, w.H, M, T, nullptr, 0, 0, 0, 0, st))) return rc;
     if ((rc = xf_gemm(LoadF32<float>{w.H, d}, L.wqkv, d, EpiBiasAct<float, 0>{L.bqkv, w.QKV, 3 * d}, M, 3 * d, d, st))) return rc;
-    if ((rc = attention(d / p->heads, w.QKV, nullptr, B, T, d, p->heads, w.O, st))) return rc;
+    if ((rc = attention(d / p->heads, w.QKV, mask, B, T, d, p->heads, w.O, st))) return rc;
     if ((rc = xf_gemm(LoadF32<float>{w.O, d}, L.wo, d, EpiBiasRes{L.bo, X, R, d}, M, d, d, st))) return rc;
     std::swap(X, R);
-    if ((rc = ln_mask(d, X, L.g2, L.b2, nullptr, w.H, M, T, nullptr, 0, 0, 0, 0, st))) return rc;
+    // the masked rows of H are 0: the k-tap FFN conv finds its zero pad at each utterance's own end
+    if ((rc = ln_mask(d, X, L.g2, L.b2, mask, w.H, M, T, nullptr, 0, 0, 0, 0, st))) return rc;
     if ((rc = xf_gemm(LoadConvRows<float, false>{w.H, d, T, p->k, 1, nullptr, 0, 0, 0.f, nullptr, nullptr}, L.w1,
                                  p->k * d, EpiBiasAct<float, 3>{L.c1b, w.Hf, F}, M, F, p->k * d, st)))
       return rc;
     if ((rc = xf_gemm(LoadF32<float>{w.Hf, F}, L.w2, F, EpiBiasRes{L.c2b, X, R, d}, M, d, F, st))) return rc;
     std::swap(X, R);
   }
-  if ((rc = ln_mask(d, X, p->lg, p->lb, nullptr, w.H, M, T, nullptr, 0, 0, 0, 0, st))) return rc;
-  hipLaunchKernelGGL(mean_t_kernel, dim3((d + 63) / 64, B), dim3(64 * kMeanWaves), 0, st, w.H, T, d, spk);
+  if ((rc = ln_mask(d, X, p->lg, p->lb, mask, w.H, M, T, nullptr, 0, 0, 0, 0, st))) return rc;
+  hipLaunchKernelGGL(mean_t_kernel<End>, dim3((d + 63) / 64, B), dim3(64 * kMeanWaves), 0, st, w.H, T, d, spk, end);
   FL_LAUNCH_CHECK();
   return kOk;
 }
@@ -287,7 +355,7 @@ FLAMED_API int flamed_vq_destroy(flamed_vq_t h) {
   {
     std::lock_guard<std::mutex> lk(p->mu);
     DeviceGuard dg(p->device);
-    p->graph.release();
+    p->release_graphs();
     if (p->dev) (void)hipFree(p->dev);
   }
   delete p;
@@ -310,12 +378,13 @@ FLAMED_API int flamed_vq_load(flamed_vq_t h, const float* const* w, int nw, hipS
   std::lock_guard<std::mutex> lk(p->mu);
   if (p->device >= 0 && p->device != wdev) {
     DeviceGuard og(p->device);
-    p->graph.release();
+    p->release_graphs();
     if (p->dev) { (void)hipFree(p->dev); p->dev = nullptr; }
   }
   p->device = wdev;
   FL_ON_DEVICE(wdev);
   p->graph.release();
+  p->graph_l.release();
   if (p->dev) { FL_HIP(hipFree(p->dev)); p->dev = nullptr; }
   const int C = p->C, cd = p->cd, d = p->d, F = p->F, k = p->k;
   // packed region: per VQ layer folded in/out weights, normalised codebook, code norms; per timbre layer
@@ -400,26 +469,75 @@ FLAMED_API int flamed_vq_ws_offsets(flamed_vq_t h, int B, int T, size_t* off) {
   return kOk;
 }
 
+// The call behind flamed_vq_encode (hlens null) and flamed_vq_encode_lens (hlens: B host lengths in frames, already
+// checked).  `who` names the entry point in error messages.
+static int vq_encode_call(PromptVq* p, const char* who, const float* x, int B, int T, const int* hlens, int64_t pad_code,
+                          float* outs, int64_t* codes, float* qbuf, float* spk, void* ws, size_t ws_bytes, int use_graph,
+                          hipStream_t st) {
+  std::lock_guard<std::mutex> lk(p->mu);
+  FL_ON_DEVICE(p->device);
+  FL_REQUIRE_ON(x, p->device, who);
+  const Tune tsnap = tune_snapshot(nullptr);
+  TuneScope ts_(&tsnap);
+  if (ws_bytes < vq_ws_layout(p, B, T, nullptr, nullptr)) {
+    set_error("%s: workspace too small", who);
+    return kNoWorkspace;
+  }
+  VqWs w;
+  vq_ws_layout(p, B, T, ws, &w);
+  std::vector<const void*> key = {x, outs, codes, qbuf, spk, ws, (const void*)(intptr_t)B, (const void*)(intptr_t)T, p->dev};
+  if (!hlens)
+    return with_graph(p->graph, key, use_graph != 0, st, [&](hipStream_t s) {
+      return run_vq<false>(p, x, B, T, outs, codes, qbuf, spk, w, s, nullptr, nullptr, 0);
+    });
+  // lengths and key mask: handle-owned, the lengths written in stream order ahead of the kernels / the replay
+  bool moved = false;
+  const int rc = p->dlens.put(hlens, B, st, &moved);
+  if (rc) return rc;
+  const size_t need = (size_t)B * T;
+  if (need > p->mask_cap) {
+    if (p->dmask) FL_HIP(hipFree(p->dmask));  // (waits for the work that may still read it)
+    p->dmask = nullptr;
+    p->mask_cap = 0;
+    FL_HIP(hipMalloc(&p->dmask, a256p(need)));
+    p->mask_cap = a256p(need);
+    moved = true;
+  }
+  if (moved) p->graph_l.retire();
+  // the graph holds no length; the pad code is a kernel argument, so it is part of the key
+  key.push_back(p->dlens.d);
+  key.push_back(p->dmask);
+  key.push_back((const void*)(intptr_t)pad_code);
+  const int* dl = p->dlens.d;
+  uint8_t* dm = p->dmask;
+  return with_graph(p->graph_l, key, use_graph != 0, st, [&](hipStream_t s) {
+    return run_vq<true>(p, x, B, T, outs, codes, qbuf, spk, w, s, dl, dm, pad_code);
+  });
+}
+
 FLAMED_API int flamed_vq_encode(flamed_vq_t h, const float* x, int B, int T, float* outs, int64_t* codes, float* qbuf,
                                 float* spk, void* ws, size_t ws_bytes, int use_graph, hipStream_t st) {
   PromptVq* p = reinterpret_cast<PromptVq*>(h);
   FL_REQUIRE(p && p->dev, "flamed_vq_encode: handle not loaded");
   FL_REQUIRE(x && outs && codes && qbuf && spk && ws && B > 0 && T > 0, "flamed_vq_encode: bad args");
   FL_REQUIRE(B <= p->pe_len, "flamed_vq_encode: B=%d exceeds the position table (%d rows)", B, p->pe_len);
-  std::lock_guard<std::mutex> lk(p->mu);
-  FL_ON_DEVICE(p->device);
-  FL_REQUIRE_ON(x, p->device, "flamed_vq_encode");
-  const Tune tsnap = tune_snapshot(nullptr);
-  TuneScope ts_(&tsnap);
-  if (ws_bytes < vq_ws_layout(p, B, T, nullptr, nullptr)) {
-    set_error("flamed_vq_encode: workspace too small");
-    return kNoWorkspace;
-  }
-  VqWs w;
-  vq_ws_layout(p, B, T, ws, &w);
-  std::vector<const void*> key = {x, outs, codes, qbuf, spk, ws, (const void*)(intptr_t)B, (const void*)(intptr_t)T, p->dev};
-  return with_graph(p->graph, key, use_graph != 0, st,
-                    [&](hipStream_t s) { return run_vq(p, x, B, T, outs, codes, qbuf, spk, w, s); });
+  return vq_encode_call(p, "flamed_vq_encode", x, B, T, nullptr, 0, outs, codes, qbuf, spk, ws, ws_bytes, use_graph, st);
+}
+
+FLAMED_API int flamed_vq_encode_lens(flamed_vq_t h, const float* x, int B, int T, const int* lens, int64_t pad_code,
+                                     float* outs, int64_t* codes, float* qbuf, float* spk, void* ws, size_t ws_bytes,
+                                     int use_graph, hipStream_t st) {
+  // every check of the arguments comes before any pointer is touched
+  FL_REQUIRE(h && x && lens && outs && codes && qbuf && spk && ws,
+             "flamed_vq_encode_lens: null handle, input, lengths, outs, codes, qbuf, spk or workspace");
+  FL_REQUIRE(B > 0 && T > 0, "flamed_vq_encode_lens: bad dims B=%d T=%d", B, T);
+  for (int u = 0; u < B; ++u)
+    FL_REQUIRE(lens[u] >= 1 && lens[u] <= T, "flamed_vq_encode_lens: utterance %d has length %d (1..T = %d)", u, lens[u], T);
+  // one full-length utterance: the dense call itself (pe[0] is pe[b] there).  B > 1 never is: the dense call adds pe[b]
+  if (B == 1 && lens[0] == T) return flamed_vq_encode(h, x, B, T, outs, codes, qbuf, spk, ws, ws_bytes, use_graph, st);
+  PromptVq* p = reinterpret_cast<PromptVq*>(h);
+  FL_REQUIRE(p->dev, "flamed_vq_encode_lens: handle not loaded");
+  return vq_encode_call(p, "flamed_vq_encode_lens", x, B, T, lens, pad_code, outs, codes, qbuf, spk, ws, ws_bytes, use_graph, st);
 }
 
 }  // extern "C"

@@ -172,16 +172,49 @@ class FACodecEncoder(nn.Module):
         return nat.supported("enc", self.ngf, len(self.up_ratios), tuple(self.up_ratios), self.out_channels,
                              nat.dtype_code(self.hip_dtype))
 
-    def forward(self, x):
-        """waveform (B, 1, n) -> (B, out_channels, T) (reference :215-217)."""
+    def out_len(self, n: int) -> int:
+        """Frames the encoder makes of n samples: Conv1d(k = 2s, stride s, pad ceil(s / 2)) at every stride, 0 where a
+        kernel does not fit its padded input (the same arithmetic as flamed_enc_out_len, on the host for both paths)."""
+        n = int(n)
+        for s in self.up_ratios:
+            span = n + 2 * (s // 2 + s % 2) - 2 * s
+            n = 0 if span < 0 else span // s + 1
+        return n
+
+    def min_len(self) -> int:
+        """The shortest input that leaves a frame (152 samples for ratios 2, 4, 5, 5)."""
+        need = 1
+        for s in reversed(self.up_ratios):
+            need = max(1, (need - 1) * s + 2 * s - 2 * (s // 2 + s % 2))
+        return need
+
+    def forward(self, x, lens=None):
+        """waveform (B, 1, n) -> (B, out_channels, T) (reference :215-217).
+
+        lens (exact lengths; B sample counts in min_len()..n, a sequence or a 1-D integer tensor): utterance u of the
+        padded batch is encoded over its own lens[u] samples, so z[u, :, :T_u] with T_u = out_len(lens[u]) is
+        forward(x[u:u+1, :, :lens[u]]) and z[u, :, T_u:] is exactly 0; nothing stored in x[u, :, lens[u]:] is read.
+        Every length equal to n is the call without lens."""
+        if lens is not None:
+            lens = check_lens(lens, x.shape[0], x.shape[2])
+            for u, n in enumerate(lens):
+                if self.out_len(n) <= 0:
+                    raise ValueError(f"lens[{u}] = {n} samples is too short for the encoder (at least {self.min_len()})")
+            if all(n == x.shape[2] for n in lens):
+                lens = None
         if self._use_hip(x):
             if self._hip is None or self._hip.dtype_name != self.hip_dtype:
                 self._hip = EncoderHIP(self, self.hip_dtype)
+            if lens is not None:
+                return ops.enc_encode_lens(self._hip.oid, x, lens)
             return ops.enc_encode(self._hip.oid, x)
+        if lens is not None:  # the definition: one utterance after another, alone
+            T = self.out_len(x.shape[2])
+            return torch.cat([F.pad(self.block(x[u:u + 1, :, :n]), (0, T - self.out_len(n))) for u, n in enumerate(lens)], dim=0)
         return self.block(x)
 
-    def inference(self, x):
-        return self.forward(x)
+    def inference(self, x, lens=None):
+        return self.forward(x, lens)
 
 
 class FACodecDecoder(nn.Module):
@@ -311,9 +344,18 @@ class FACodecDecoder(nn.Module):
         return outs, torch.cat(qs, dim=0), torch.cat(losses, dim=0), qbuf
 
     def forward(self, x, vq=True, get_vq=False, eval_vq=True, speaker_embedding=None, n_quantizers=None,
-                quantized=None):
+                quantized=None, lens=None, pad_code=None):
         """Prompt encoding (reference :509-530): encoder output (B, C, T) ->
-        (quantized sum, codes (n_q, B, T), commit losses, per-RVQ quantized, speaker embedding (B, C))."""
+        (quantized sum, codes (n_q, B, T), commit losses, per-RVQ quantized, speaker embedding (B, C)).
+
+        lens (exact lengths; B frame counts in 1..T): utterance u of the padded batch is quantized and its speaker
+        embedding taken over its own lens[u] frames, as forward(x[u:u+1, :, :lens[u]]) gives them; behind its end the
+        quantized tensors are exactly 0 and the codes are pad_code (default: the codebook size, the prior's vocab_size,
+        which pad_prompts uses); nothing stored in x[u, :, lens[u]:] is read.  POSITION ROW: without lens the timbre
+        encoder keeps the reference's `x + pe[:B]`, which indexes the position table by the batch index, so utterance b
+        gets pe[b] and not even equal-length prompts get their solo speaker embedding.  With lens every utterance gets
+        pe[0], the row it gets alone; for B > 1 the call with lens is therefore never the call without, not even with
+        every length equal to T.  At B = 1 with lens[0] == T it is the call without lens."""
         if get_vq:
             return self.quantizer.get_emb() if hasattr(self.quantizer, "get_emb") else [q.get_emb() for q in self.quantizer]
         if vq is not True:
@@ -321,12 +363,32 @@ class FACodecDecoder(nn.Module):
                                       "which this build does not implement")
         if eval_vq:
             self.quantizer.eval()
+        if lens is not None:
+            lens = check_lens(lens, x.shape[0], x.shape[2])
+            if pad_code is None:
+                pad_code = max(q.layers[0]._codebook.weight.shape[0] for q in self.quantizer)
+            if len(lens) == 1 and lens[0] == x.shape[2]:
+                lens = None
         if self._vq_hip_ok(x, n_quantizers):
             if self._vq_hip is None:
                 self._vq_hip = VqHIP(self)
-            outs, qs, qb, spk = ops.vq_encode(self._vq_hip.oid, x)
+            if lens is not None:
+                outs, qs, qb, spk = ops.vq_encode_lens(self._vq_hip.oid, x, lens, int(pad_code))
+            else:
+                outs, qs, qb, spk = ops.vq_encode(self._vq_hip.oid, x)
             commit_loss = torch.zeros(qs.shape[0], device=x.device)
             return outs, qs, commit_loss, list(qb.unbind(0)), spk
+        if lens is not None:  # the definition: one utterance after another, alone (each at batch index 0: pe[0])
+            T = x.shape[2]
+            solo = [self._forward_torch(x[u:u + 1, :, :n], n_quantizers) for u, n in enumerate(lens)]
+            outs = torch.cat([F.pad(r[0], (0, T - n)) for r, n in zip(solo, lens)], dim=0)
+            qs = torch.cat([F.pad(r[1], (0, T - n), value=int(pad_code)) for r, n in zip(solo, lens)], dim=1)
+            commit_loss = torch.stack([r[2] for r in solo]).mean(0)
+            qbuf = [torch.cat([F.pad(r[3][g], (0, T - n)) for r, n in zip(solo, lens)], dim=0) for g in range(len(self.quantizer))]
+            return outs, qs, commit_loss, qbuf, torch.cat([r[4] for r in solo], dim=0)
+        return self._forward_torch(x, n_quantizers)
+
+    def _forward_torch(self, x, n_quantizers):
         outs, qs, commit_loss, qbuf = self.quantize(x, n_quantizers=n_quantizers)
         spk = self.timbre_encoder(x.transpose(1, 2), None, None).transpose(1, 2).mean(dim=2)
         return outs, qs, commit_loss, qbuf, spk
@@ -558,9 +620,12 @@ class EncoderHIP:
         self._ensure_created()
         return int(nat.lib().flamed_enc_out_len(self.handle, n))
 
-    def encode(self, x):
+    def encode(self, x, lens=None):
+        """lens: None, or B sample counts (flamed_enc_encode_lens: each utterance over its own samples, 0 behind it)."""
         if x.dim() != 3 or x.shape[1] != 1:
             raise ValueError(f"FACodecEncoder expects (B, 1, n) audio, got {tuple(x.shape)}")
+        if lens is not None:
+            lens = check_lens(lens, x.shape[0], x.shape[2])
         dev = x.device
         self._ensure(dev)
         B, _, n = x.shape
@@ -576,6 +641,11 @@ class EncoderHIP:
             self._bufs = {key: bufs}
         bufs["x"].copy_(x.reshape(B, n))
         ws = self.ws.get(L.flamed_enc_workspace_size(self.handle, B, n), dev)
+        if lens is not None:
+            nat.check(L.flamed_enc_encode_lens(self.handle, nat.ptr(bufs["x"]), B, n, (ctypes.c_int * B)(*lens),
+                                               nat.ptr(bufs["out"]), nat.ptr(ws), ws.numel(), int(bool(self.enc.hip_graph)),
+                                               nat.stream_ptr(dev)), "flamed_enc_encode_lens")
+            return bufs["out"].clone()
         nat.check(L.flamed_enc_encode(self.handle, nat.ptr(bufs["x"]), B, n, nat.ptr(bufs["out"]), nat.ptr(ws), ws.numel(),
                                       int(bool(self.enc.hip_graph)), nat.stream_ptr(dev)), "flamed_enc_encode")
         return bufs["out"].clone()
@@ -648,9 +718,12 @@ class VqHIP:
         self._sig = sig
         self._bufs = {}
 
-    def encode(self, x: torch.Tensor):
+    def encode(self, x: torch.Tensor, lens=None, pad_code: int = 0):
         """x (B, C, T) encoder output -> (outs (B, C, T), codes (n_q, B, T) int64, per-group quantized sums
-        (G, B, C, T), speaker embedding (B, C))."""
+        (G, B, C, T), speaker embedding (B, C)).  lens: None, or B frame counts in 1..T (flamed_vq_encode_lens: each
+        utterance over its own frames with position row pe[0]; 0 / pad_code behind its end)."""
+        if lens is not None:
+            lens = check_lens(lens, x.shape[0], x.shape[2])
         dev = x.device
         self._ensure(dev)
         B, C, T = x.shape
@@ -668,6 +741,12 @@ class VqHIP:
         bufs["x"].copy_(x)
         L = nat.lib()
         ws = self.ws.get(L.flamed_vq_workspace_size(self.handle, B, T), dev)
+        if lens is not None:
+            nat.check(L.flamed_vq_encode_lens(self.handle, nat.ptr(bufs["x"]), B, T, (ctypes.c_int * B)(*lens),
+                                              ctypes.c_int64(int(pad_code)), nat.ptr(bufs["outs"]), nat.ptr(bufs["codes"]),
+                                              nat.ptr(bufs["qbuf"]), nat.ptr(bufs["spk"]), nat.ptr(ws), ws.numel(),
+                                              int(bool(self.dec.hip_graph)), nat.stream_ptr(dev)), "flamed_vq_encode_lens")
+            return tuple(bufs[k].clone() for k in ("outs", "codes", "qbuf", "spk"))
         nat.check(L.flamed_vq_encode(self.handle, nat.ptr(bufs["x"]), B, T, nat.ptr(bufs["outs"]), nat.ptr(bufs["codes"]),
                                      nat.ptr(bufs["qbuf"]), nat.ptr(bufs["spk"]), nat.ptr(ws), ws.numel(),
                                      int(bool(self.dec.hip_graph)), nat.stream_ptr(dev)), "flamed_vq_encode")

@@ -167,6 +167,30 @@ class Flamed(nn.Module):
             outputs["wav"] = codec_decoder.inference(latents, timbres)
         return outputs
 
+    @torch.inference_mode()
+    def encode_prompts(self, prompts, sr: int = 16000, codec_encoder=None, codec_decoder=None):
+        """A batch of raw prompts (paths / np.ndarrays / 1-D tensors of samples, any lengths) through the prompt stage
+        with exact lengths: ONE ragged encoder call (FACodecEncoder.forward(x, lens)), ONE ragged quantizer / timbre
+        call (FACodecDecoder.forward(..., lens, pad_code = vocab_size)) and no host sync of its own (the frame counts
+        are host arithmetic, FACodecEncoder.out_len), so the caller's copy of the result is the only one.  Every prompt gets the codes and the speaker embedding it gets
+        alone.  Returns (prompts (B, n_q, P) int64 padded with vocab_size, prompt_lens (list of B ints), timbres
+        (B, C)): what sample_batch(prompts=..., timbres=..., prompt_lens=...) takes."""
+        if codec_encoder is None or codec_decoder is None:
+            raise ValueError("encode_prompts needs a codec_encoder and a codec_decoder")
+        if len(prompts) == 0:
+            raise ValueError("encode_prompts needs at least one prompt")
+        wavs = [self._preprocess_acoustic_prompt(p, sr).reshape(-1) for p in prompts]
+        lens = [int(w.numel()) for w in wavs]
+        n = max(lens)
+        wav = torch.zeros((len(wavs), 1, n), dtype=torch.float32, device=self.device)
+        for u, w in enumerate(wavs):
+            wav[u, 0, :lens[u]] = w
+        pad = self.prior_generator.code_embedding.padding_idx
+        z = codec_encoder(wav, lens=lens)
+        prompt_lens = [codec_encoder.out_len(m) for m in lens]
+        _, codes, _, _, timbres = codec_decoder(z, eval_vq=False, vq=True, lens=prompt_lens, pad_code=pad)
+        return codes.permute(1, 0, 2).contiguous(), prompt_lens, timbres
+
     def _prompt_lens_from_pad(self, prompts):
         """Per-utterance prompt lengths of a (B, n_q, P) batch of codes padded with the pad id vocab_size."""
         pad = self.prior_generator.code_embedding.padding_idx

@@ -27,6 +27,9 @@ take tensors and scalars only); the registry holds weak references, so a dropped
                                                    padded batch decoded over its own frames, as if alone; 0 behind it
   flamed_hip::enc_encode(id, x)                    FACodecEncoder.forward          facodec.py:158-243
   flamed_hip::vq_encode(id, x)                     FACodecDecoder.forward(vq=True) facodec.py:470-533
+  flamed_hip::enc_encode_lens(id, x, lens)         exact lengths in the prompt stage (no reference counterpart): every
+  flamed_hip::vq_encode_lens(id, x, lens, pad_code)  prompt of the padded batch encoded / quantized over its own samples /
+                                                   frames, as if alone (position row pe[0] for every utterance)
   flamed_hip::prior_encode(id, texts, mask)        Encoder.forward (prior)         prior_generator.py:152-153
   flamed_hip::prior_decode(id, x, mask, prompts, P) bridge + decoders + head       prior_generator.py:165-188
 
@@ -241,6 +244,32 @@ def _(oid, x):
             x.new_empty((B, C)))
 
 
+@torch.library.custom_op("flamed_hip::enc_encode_lens", mutates_args=())
+def enc_encode_lens(oid: int, x: Tensor, lens: List[int]) -> Tensor:
+    return owner(oid).encode(x, lens=lens)
+
+
+@enc_encode_lens.register_fake
+def _(oid, x, lens):
+    o = owner(oid)
+    B, _, n = x.shape
+    return x.new_empty((B, o.enc.out_channels, o.out_len(n)), dtype=torch.float32)
+
+
+@torch.library.custom_op("flamed_hip::vq_encode_lens", mutates_args=())
+def vq_encode_lens(oid: int, x: Tensor, lens: List[int], pad_code: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    return owner(oid).encode(x, lens=lens, pad_code=pad_code)
+
+
+@vq_encode_lens.register_fake
+def _(oid, x, lens, pad_code):
+    B, C, T = x.shape
+    q = owner(oid).dec.quantizer
+    nq = sum(len(r.layers) for r in q)
+    return (x.new_empty((B, C, T)), x.new_empty((nq, B, T), dtype=torch.int64), x.new_empty((len(q), B, C, T)),
+            x.new_empty((B, C)))
+
+
 # ---------------------------------------------------------------- prior transformer stack
 
 @torch.library.custom_op("flamed_hip::prior_encode", mutates_args=())
@@ -283,4 +312,4 @@ def _(oid, x, tgt_mask, prompts, prompts_len, prompt_lens):
 
 OPS = ("den_velocity", "den_solve", "den_solve_rk2", "den_solve_lens", "den_solve_rk2_lens", "cond_fold", "cond_fold_exact",
        "pva_flow", "length_regulate", "fac_decode", "fac_decode_lens", "enc_encode", "vq_encode", "prior_encode", "prior_decode",
-       "pva_flow_exact", "length_regulate_exact", "prior_decode_lens")
+       "pva_flow_exact", "length_regulate_exact", "prior_decode_lens", "enc_encode_lens", "vq_encode_lens")

@@ -134,6 +134,20 @@ def encode_prompt_features(model: Flamed, codec_encoder, codec_decoder, prompt_p
     return cache[prompt_path]
 
 
+def encode_prompt_batch(model: Flamed, codec_encoder, codec_decoder, prompt_paths: List[str],
+                        cache: Dict[str, Tuple[torch.Tensor, torch.Tensor]]) -> None:
+    """--batch-prompts: the uncached prompts of a batch (each path once) through Flamed.encode_prompts -- one ragged
+    encoder call, one ragged quantizer / timbre call and one device-to-host copy -- into the per-path cache, each with
+    the codes and the timbre it gets alone (encode_prompt_features then finds every path cached)."""
+    todo = [p for p in dict.fromkeys(prompt_paths) if p not in cache]
+    if not todo:
+        return
+    codes, lens, timbres = model.encode_prompts(todo, sr=SR, codec_encoder=codec_encoder, codec_decoder=codec_decoder)
+    codes, timbres = codes.detach().cpu(), timbres.detach().cpu()
+    for u, path in enumerate(todo):
+        cache[path] = (codes[u, :, :lens[u]].contiguous(), timbres[u].contiguous())
+
+
 def pad_prompts(prompt_tensors: List[torch.Tensor], pad_value: int, device: torch.device):
     if not prompt_tensors:
         raise ValueError("pad_prompts received an empty list.")
@@ -147,10 +161,13 @@ def pad_prompts(prompt_tensors: List[torch.Tensor], pad_value: int, device: torc
 
 
 def build_metadata_batch(model: Flamed, codec_encoder, codec_decoder, batch_items: List[Dict[str, str]],
-                         prompt_cache: Dict[str, Tuple[torch.Tensor, torch.Tensor]]):
+                         prompt_cache: Dict[str, Tuple[torch.Tensor, torch.Tensor]], batch_prompts: bool = False):
     """(phonemes (B, L) zero-padded, src_lens, prompts (B, 6, P) padded with the codec vocab size,
-    timbres (B, 256)) (reference :162-191)."""
+    timbres (B, 256)) (reference :162-191).  batch_prompts: the batch's uncached prompts are encoded in one ragged
+    call pair first (encode_prompt_batch); without it each is encoded alone, as the reference does."""
     phonemes, src_lens, prompts, timbres = [], [], [], []
+    if batch_prompts:
+        encode_prompt_batch(model, codec_encoder, codec_decoder, [it["prompt_path"] for it in batch_items], prompt_cache)
     for item in batch_items:
         seq = model._preprocess_english(item["text"])[0].squeeze(0)
         phonemes.append(seq)
@@ -228,13 +245,14 @@ def synthesize_with_metadata(model: Flamed, codec_encoder, codec_decoder, metada
                              output_dir: str, nsteps_durgen: int, nsteps_denoiser: int, temp_durgen: float,
                              temp_denoiser: float, skip_existing: bool, batch_size: int,
                              meter: Optional[RtfMeter] = None, solver_denoiser: str = "euler",
-                             exact_lengths: bool = False, exact_prior: bool = False):
+                             exact_lengths: bool = False, exact_prior: bool = False, batch_prompts: bool = False):
     """Batched `Flamed.sample_batch` over a `target|prompt|text` file (reference :220-303).  A denoiser solver
     other than Euler is appended to the target directory's name, and `-exact` for exact lengths (every utterance of
     a padded batch then gets the latents and the waveform it would get alone, and its file is trimmed to its own
     length, out["wav_lens"]; without the flag every file of a batch has the batch's padded length), and `-xprior` for
     the exact prior stage (durations, frame counts and prior embeddings as if alone; the prompts' own lengths are
-    read from the pad id that build_metadata_batch pads them with)."""
+    read from the pad id that build_metadata_batch pads them with).  batch_prompts: the uncached prompts of a batch
+    are encoded together with exact lengths (same file names: every prompt gets what it gets alone)."""
     with open(metadata_file, "r", encoding="utf-8") as fin:
         entries = [line.strip() for line in fin if line.strip()]
     target_dir = os.path.join(output_dir, f"nfe{nsteps_denoiser}-temp{temp_denoiser}{_solver_suffix(solver_denoiser, exact_lengths, exact_prior)}")
@@ -261,7 +279,8 @@ def synthesize_with_metadata(model: Flamed, codec_encoder, codec_decoder, metada
         return None
     for batch in _progress(chunked(pending, batch_size), total=math.ceil(len(pending) / batch_size),
                            desc="Synthesizing metadata entries"):
-        phonemes, src_lens, prompts, timbres = build_metadata_batch(model, codec_encoder, codec_decoder, batch, cache)
+        phonemes, src_lens, prompts, timbres = build_metadata_batch(model, codec_encoder, codec_decoder, batch, cache,
+                                                                    **({"batch_prompts": True} if batch_prompts else {}))
         out = model.sample_batch(phonemes=phonemes, src_lens=src_lens, prompts=prompts, timbres=timbres,
                                  codec_decoder=codec_decoder, temp_durgen=temp_durgen, temp_denoiser=temp_denoiser,
                                  nsteps_durgen=nsteps_durgen, nsteps_denoiser=nsteps_denoiser,
@@ -325,6 +344,9 @@ def build_arg_parser():
                         "padded batch over its own phonemes and behind its own prompt, so its durations, its frame "
                         "count and its prior embeddings do not depend on the batch it shares; with --exact-lengths a "
                         "file no longer depends on the other lines of its batch (default: False).")
+    p.add_argument("--batch-prompts", type=str2bool, default=False,
+                   help="Metadata mode: encode the uncached prompts of a batch in one ragged call pair with exact lengths "
+                        "(each prompt gets the codes and the timbre it gets alone) instead of one after another.")
     p.add_argument("--temp-durgen", type=float, default=0.3, help="Duration generator temperature.")
     p.add_argument("--temp-denoiser", type=float, default=0.3, help="Denoiser temperature.")
     p.add_argument("--device", type=str, default="cuda:0", help="Device to run inference on.")
@@ -365,7 +387,8 @@ def main(args: Optional[argparse.Namespace] = None):
                   exact_prior=bool(getattr(args, "exact_prior", False)))
     if args.metadata_file:
         rtf = synthesize_with_metadata(metadata_file=args.metadata_file, skip_existing=args.skip_existing,
-                                       batch_size=args.batch_size, **common)
+                                       batch_size=args.batch_size, **common,
+                                       **({"batch_prompts": True} if getattr(args, "batch_prompts", False) else {}))
     else:
         rtf = synthesize_with_prompts(text=args.text, prompt_list=args.prompt_list, **common)
     if distributed:  # every rank's records; each rank's frames/s summed over the ranks' wall time

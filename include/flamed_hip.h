@@ -425,6 +425,20 @@ FLAMED_API size_t flamed_enc_workspace_size(flamed_enc_t h, int B, int n);
 /* wav: (B, n) fp32 (the reference's (B, 1, n)); out: (B, out_channels, flamed_enc_out_len(n)) fp32. */
 FLAMED_API int flamed_enc_encode(flamed_enc_t h, const float* wav, int B, int n, float* out, void* ws, size_t ws_bytes,
                                  int use_graph, hipStream_t stream);
+/* Exact lengths: the same encode for a padded ragged batch of prompts.  lens: B HOST ints in samples, min_n <= lens[u]
+ * <= n (read before the call returns), min_n being the shortest input with flamed_enc_out_len > 0 (152 for ratios
+ * 2, 4, 5, 5).  Utterance u is encoded over its own lens[u] samples exactly as if it were alone at n = lens[u]: every
+ * zero pad, replicate pad and strided tap is cut at its own end at every stage (the stage lengths follow the Conv1d
+ * arithmetic per utterance, which is not linear in the length; the host computes the table and it travels to a
+ * handle-owned device array in stream order ahead of the kernels).  out[u, :, : T_u] with T_u = flamed_enc_out_len(
+ * lens[u]) is that result and out[u, :, T_u :] is written as 0; nothing stored in wav[u, lens[u] :] is read (NaN and
+ * inf included).  Every length equal to n is flamed_enc_encode itself (same kernels, same graph, bitwise).  The ragged
+ * call keeps a hipGraph of its own, which holds the table's address and no length: one capture serves every ragged
+ * call of the same pointers and (B, n).  Workspace as for flamed_enc_encode; one call at a time per handle, as there.
+ * A null pointer or a length outside min_n..n returns 1001 with a flamed_last_error text before any pointer is
+ * touched. */
+FLAMED_API int flamed_enc_encode_lens(flamed_enc_t h, const float* wav, int B, int n, const int* lens, float* out, void* ws,
+                                      size_t ws_bytes, int use_graph, hipStream_t stream);
 
 /* ======================= prior transformer stack (once per utterance) =======================
  * Replaces the transformer parts of PriorGenerator.sample (prior_generator.py:141-196, SURVEY.md §8(f)
@@ -501,6 +515,20 @@ FLAMED_API size_t flamed_vq_workspace_size(flamed_vq_t h, int B, int T);
  * qbuf (G, B, C, T) per-group quantized sums, spk (B, C) speaker embedding. */
 FLAMED_API int flamed_vq_encode(flamed_vq_t h, const float* x, int B, int T, float* outs, int64_t* codes, float* qbuf,
                                 float* spk, void* ws, size_t ws_bytes, int use_graph, hipStream_t stream);
+/* Exact lengths: the same for a padded ragged batch.  lens: B HOST ints in frames, 1 <= lens[u] <= T (read before the
+ * call returns).  Utterance u is quantized and its speaker embedding taken over its own lens[u] frames exactly as if
+ * it were alone at T = lens[u]: the attention keys, the FFN conv's zero pad and the time mean end at its own end.
+ * outs / qbuf behind an end are written as 0 and codes as pad_code; nothing stored in x[u, :, lens[u] :] is read (NaN
+ * and inf included).  POSITION ROW: flamed_vq_encode keeps the reference's `x + pe[:B]`, which indexes the position
+ * table by the BATCH index, so there utterance b gets pe[b] and even equal-length prompts do not get their solo speaker
+ * embedding; this call adds pe[0] to EVERY utterance, which is what each gets alone.  For B > 1 it is therefore never
+ * the dense call, not even with every length equal to T (and B is not bounded by the position table's rows); at B = 1
+ * with lens[0] == T it is flamed_vq_encode itself (same kernels, same graph, bitwise).  The ragged call keeps a
+ * hipGraph of its own, which holds no length.  Workspace as for flamed_vq_encode; one call at a time per handle.  A null
+ * pointer or a length outside 1..T returns 1001 with a flamed_last_error text before any pointer is touched. */
+FLAMED_API int flamed_vq_encode_lens(flamed_vq_t h, const float* x, int B, int T, const int* lens, int64_t pad_code,
+                                     float* outs, int64_t* codes, float* qbuf, float* spk, void* ws, size_t ws_bytes,
+                                     int use_graph, hipStream_t stream);
 
 #ifdef __cplusplus
 }
