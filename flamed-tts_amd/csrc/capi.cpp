@@ -91,7 +91,7 @@ int tune_apply(Tune& t, const char* key, int value) {
       {"split_prio", &Tune::split_prio, 0, 2, nullptr},
       {"prio_all", &Tune::prio_all, 0, 1, nullptr},
       {"split_min_rows", &Tune::split_min_rows, 1024, 1 << 30, nullptr},
-      {"persist_opt", &Tune::persist_opt, 0, (1 << 22) - 1, nullptr},  // up to bit 2097152; bit 1048576 is unused
+      {"persist_opt", &Tune::persist_opt, 0, (1 << 23) - 1, nullptr},  // up to bit 4194304; bit 1048576 is unused
       {"persist_seal_skip", &Tune::persist_seal_skip, -1, 1 << 20, nullptr},
       {"persist_inject", &Tune::persist_inject, -1, 1 << 20, nullptr},
       {"persist_multi", &Tune::persist_multi, 0, 1, nullptr},
@@ -110,6 +110,7 @@ int tune_apply(Tune& t, const char* key, int value) {
       {"dwgn_var", &Tune::dwgn_var, 0, 2, nullptr},
       {"pva_stage", &Tune::pva_stage, 0, 3, nullptr},
       {"pva_inject", &Tune::pva_inject, -1, 1 << 20, nullptr},
+      {"adaln_grouped", &Tune::adaln_grouped, 0, 1, nullptr},
   };
   for (const Knob& k : knobs) {
     if (std::strcmp(k.name, key) != 0) continue;

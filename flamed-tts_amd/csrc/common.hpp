@@ -217,6 +217,10 @@ struct Tune {
                            // 1024 2 x 2 wave split, 4096 drain behind the DMA, 2097152 selects the old row-major
                            // LayerNorm row partials (default: tile-major, persist.hpp xpart_off: B = 1 T = 400
                            // 20,846 -> 21,838 latent frames/s, profiles/rowpart_tiles_ab.txt);
+                           // 4194304 selects one arrival word per row group for the group hand-offs (default: four, one
+                           // per eight slots, each on its own 128-B line; persist.hpp arrive_image: launch_ms 17.65 ->
+                           // 16.85, profiles/arrive_shard_ab.txt); the kernel variants of pk::one_word_variant keep the
+                           // one word at compile time, so the bit selects nothing there;
                            // 1048576 is unused.  Removed after measuring: the GEMM
                            // phases' deferred seal loads issued after the GEMM (r06ap neutral as a bit, but its code
                            // slowed the default kernel 2-5 %, r06ar)
@@ -230,6 +234,8 @@ struct Tune {
   int pva_inject = -1;     // diagnostic: every persistent PVA flow fails at this step (-1 = never)
   int dwgn_var = 1;        // dwgn kernel variant: 1 scalar fp32 pair math (default), diagnostics for T in (384, 448]: 0 packed, 2 scalar LDS accesses
   int coop = 1;            // persistent kernels as cooperative launches (0: plain launches, for profiling runs)
+  int adaln_grouped = 1;   // AdaLN table (flamed_den_adaln): t0 + speaker projection and the NB + 1 fold GEMMs of each kind as
+                           // grouped launches (15 launches -> 6); 0 = one launch per GEMM (A/B, bitwise the same table)
   int stop_after = -1;     // diagnostic: a denoiser evaluation returns after this many kernel-class launches (-1 = never)
 };
 int tune_apply(Tune& t, const char* key, int value);  // kOk or kBadArg (message set)

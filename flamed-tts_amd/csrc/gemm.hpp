@@ -139,9 +139,11 @@ __device__ __forceinline__ int lds_off(int r, int c) {
 
 // NSTAGE = 2: LDS double buffer, loads issued one K-step ahead.
 // NSTAGE = 3: LDS ring of 3, two register stages, loads issued two K-steps ahead (small-M latency).
+// The tile code of one workgroup (tile blockIdx.x, blockIdx.y; K slice `kz` of sk.n), shared by the plain and the
+// grouped kernel below.
 template <int BM, int BN, int KCH, int NSTAGE, typename DT, class AL, class EP>
-__global__ __launch_bounds__(kGemmThreads) void gemm_kernel(AL al, const DT* __restrict__ W, int ldw, EP ep,
-                                                             int M, int N, int K, SplitK sk) {
+__device__ __forceinline__ void gemm_tile(const AL& al, const DT* __restrict__ W, int ldw, const EP& ep, int M, int N,
+                                          int K, const SplitK& sk, int kz) {
   using SM = GemmSmem<BM, BN, KCH, NSTAGE, AL, EP>;
   constexpr int EPC = DTraits<DT>::EPC;
   constexpr int BKE = KCH * EPC;
@@ -180,7 +182,7 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_kernel(AL al, const DT* __r
   typename AL::Raw ra0[ACH], ra1[ACH];
   u32x4 rb0[BCH], rb1[BCH];
   const int kslice = K / sk.n;
-  const int k0 = blockIdx.z * kslice;
+  const int k0 = kz * kslice;
   const int nsteps = kslice / BKE;
 
   auto issue = [&](int s, typename AL::Raw (&ra)[ACH], u32x4 (&rb)[BCH]) __attribute__((always_inline)) {
@@ -367,7 +369,7 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_kernel(AL al, const DT* __r
     const int tile = ty * gridDim.x + tx;
     float* slabs = sk.slab + (size_t)tile * sk.n * (BM * BN);
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(slabs, 0, sk.n * BM * BN * 4, 0x00020000);
-    const int mine = blockIdx.z * (BM * BN * 4);
+    const int mine = kz * (BM * BN * 4);
 #pragma unroll
     for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -483,6 +485,36 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_kernel(AL al, const DT* __r
         if (m < M) ep_store(ep, m, n, val[i][j][r], e_vec, e_uv, bm, bn);
       }
   FL_STAMP(4);
+}
+
+template <int BM, int BN, int KCH, int NSTAGE, typename DT, class AL, class EP>
+__global__ __launch_bounds__(kGemmThreads) void gemm_kernel(AL al, const DT* __restrict__ W, int ldw, EP ep,
+                                                             int M, int N, int K, SplitK sk) {
+  gemm_tile<BM, BN, KCH, NSTAGE, DT, AL, EP>(al, W, ldw, ep, M, N, K, sk, blockIdx.z);
+}
+
+// Grouped form: up to kMaxGroup independent GEMMs of one loader / epilogue type in one launch.  blockIdx.z picks the
+// problem; the grid covers the largest M and N of the group, and a workgroup beyond its own problem's tiles exits
+// before any load.  The descriptors travel by value in the kernel arguments.  No split-K, no tile re-placement: each
+// output element sees the tile code and K order of its own plain launch.
+constexpr int kMaxGroup = 8;
+template <typename DT, class AL, class EP>
+struct GemmProb {
+  AL al;
+  const DT* W;
+  int ldw;
+  EP ep;
+  int M, N, K;
+};
+template <typename DT, class AL, class EP>
+struct GemmGroup {
+  GemmProb<DT, AL, EP> p[kMaxGroup];
+};
+template <int BM, int BN, int KCH, int NSTAGE, typename DT, class AL, class EP>
+__global__ __launch_bounds__(kGemmThreads) void gemm_group_kernel(GemmGroup<DT, AL, EP> grp) {
+  const GemmProb<DT, AL, EP>& pb = grp.p[blockIdx.z];
+  if ((int)blockIdx.x * BN >= pb.N || (int)blockIdx.y * BM >= pb.M) return;  // blockIdx-uniform
+  gemm_tile<BM, BN, KCH, NSTAGE, DT, AL, EP>(pb.al, pb.W, pb.ldw, pb.ep, pb.M, pb.N, pb.K, SplitK{1, nullptr, nullptr, 0}, 0);
 }
 
 // ------------------------------ generic loaders ------------------------------
@@ -772,6 +804,49 @@ inline int launch_gemm_auto(GemmCfg c, bool wide_a, const AL& al, const DT* W, i
   if (c == kCfgLarge && wide_a && N % 128 == 0 && !EP::kRowStats)
     return launch_gemm_cfg<128, 128, 3, DT>(al, W, ldw, ep, M, N, K, st);
   return launch_gemm_auto<DT>(c, al, W, ldw, ep, M, N, K, st);
+}
+
+// Grouped launch of n <= kMaxGroup problems on the tile configuration their rows select (the caller passes problems
+// whose pick_cfg agrees, so each runs on the tiles its own launch_gemm would use).
+template <int BM, int BN, int NSTAGE, typename DT, class AL, class EP>
+inline int launch_gemm_group_cfg(const GemmProb<DT, AL, EP>* pr, int n, hipStream_t st) {
+  constexpr int KCH = 8;
+  constexpr int BKE = KCH * DTraits<DT>::EPC;
+  static_assert(kvec_of<AL>::value == 0, "grouped gemm: loaders without per-column LDS vectors");
+  using SM = GemmSmem<BM, BN, KCH, NSTAGE, AL, EP>;
+  FL_REQUIRE(n >= 1 && n <= kMaxGroup, "gemm group: %d problems", n);
+  GemmGroup<DT, AL, EP> grp{};
+  int gx = 0, gy = 0;
+  for (int i = 0; i < n; ++i) {
+    const auto& p = pr[i];
+    FL_REQUIRE(p.M > 0 && p.N % BN == 0 && p.K % BKE == 0, "gemm group: unsupported shape M=%d N=%d K=%d (BN=%d BK=%d)", p.M,
+               p.N, p.K, BN, BKE);
+    grp.p[i] = p;
+    gx = std::max(gx, p.N / BN);
+    gy = std::max(gy, (p.M + BM - 1) / BM);
+  }
+  auto kern = gemm_group_kernel<BM, BN, KCH, NSTAGE, DT, AL, EP>;
+  const size_t bytes = SM::bytes;
+  FL_REQUIRE(bytes <= 160 * 1024, "gemm group: LDS request %zu B too large", bytes);
+  if (bytes > 64 * 1024) FL_HIP(set_max_lds(reinterpret_cast<const void*>(kern)));
+  hipLaunchKernelGGL(kern, dim3(gx, gy, n), dim3(kGemmThreads), bytes, st, grp);
+  FL_LAUNCH_CHECK();
+  return kOk;
+}
+template <typename DT, class AL, class EP>
+inline int launch_gemm_group(const GemmProb<DT, AL, EP>* pr, int n, hipStream_t st) {
+  // no split-K and no strip placement in the grouped kernel: inside a SplitScope a plain launch could split K, and
+  // the promise of each problem's own K order would not hold
+  FL_REQUIRE(g_split == nullptr, "gemm group: not inside a split-K scope");
+  const GemmCfg c = pick_cfg(pr[0].M);
+  for (int i = 1; i < n; ++i) FL_REQUIRE(pick_cfg(pr[i].M) == c, "gemm group: problems of different tile configurations");
+  if (c == kCfgSmall) {
+    if (tn().small_stages == 5) return launch_gemm_group_cfg<32, 64, 5, DT>(pr, n, st);
+    if (tn().small_stages == 7) return launch_gemm_group_cfg<32, 64, 7, DT>(pr, n, st);
+    return launch_gemm_group_cfg<32, 64, 3, DT>(pr, n, st);
+  }
+  if (c == kCfgMid) return launch_gemm_group_cfg<64, 64, 3, DT>(pr, n, st);
+  return launch_gemm_group_cfg<128, 64, 3, DT>(pr, n, st);
 }
 
 // Shape-driven convenience: choose the config from M (row partial width = cfg_bn(pick_cfg(M)) when

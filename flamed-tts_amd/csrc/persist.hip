@@ -113,9 +113,12 @@ __device__ __forceinline__ void raise_err(int* err, int* fails, int code) {
     __hip_atomic_fetch_add(fails, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Wave 0 polls n counters (base + k * stride, k < n) with sc1 loads until all reach `target` (s_sleep
+// Wave 0 polls n <= 32 counters (base + k * stride, k < n) with sc1 loads until all reach `target` (s_sleep
 // between polls); bounded by P.tmo, and an error word set by any workgroup ends every wait.  The
 // other waves meet it at a barrier.  Returns false when the solve is being abandoned.
+// OPQ: the polled word's address is formed here, at the wait, from an opaque lane index, not kept in registers across
+// the solve (the sharded variants; the one-word variants keep the code they have always had).
+template <bool OPQ = false>
 __device__ __forceinline__ bool wait_ge(int* err, int* fails, long long tmo, int* base, int stride, int n, int target, int* flag) {
   if (threadIdx.x < 64) {
     const int lane = threadIdx.x;
@@ -123,7 +126,7 @@ __device__ __forceinline__ bool wait_ge(int* err, int* fails, long long tmo, int
     bool ok = true;
     for (unsigned it = 0;; ++it) {
       bool mine = true;
-      if (lane < n) mine = __hip_atomic_load(base + lane * stride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= target;
+      if (lane < n) mine = __hip_atomic_load(base + (OPQ ? opq(lane) : lane) * stride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= target;
       // the last lane watches the error word in the same poll: a wait whose counters are already complete still
       // stops once any workgroup has given the launch up (a deferred seal check, persist_opt 65536, fails
       // without stalling anyone)
@@ -910,8 +913,16 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
   float* red = reinterpret_cast<float*>(smem + L_RED);
   float4* gnv = reinterpret_cast<float4*>(smem + L_GNV);
   int* flag = reinterpret_cast<int*>(smem + L_FLAG);
-  int* grp = P.ctr + CT_GRP;
-  int* mygrp = grp + 16 * g;
+  // group hand-off words of this workgroup, fixed for the launch: persist.hpp arrive_image, or for the variants of
+  // one_word_variant the single word per group as compile-time constants
+  constexpr bool kOneWord = one_word_variant(KH, NTW, RK2, RAG);
+  const ArriveImage ai = arrive_image(kOneWord ? kOptOneWord : P.opt, g, s);
+  int* const grp = P.ctr + (kOneWord ? CT_GRP : ai.abase());
+  int* const mygrp = kOneWord ? grp + 16 * g : P.ctr + ai.base;
+  int* const mysig = kOneWord ? mygrp : P.ctr + ai.sig;
+  const int gws = kOneWord ? 0 : ai.stride(), gwn = kOneWord ? 1 : ai.n();
+  const int aws = kOneWord ? 16 : ai.stride(), awn = kOneWord ? kGroups : ai.an();
+  auto gtarget = [&](int l) { return kOneWord ? 32 * l : ai.target(l); };
   int* gnc = P.ctr + CT_GN + 16 * s;
   int* errw = P.ctr + CT_ERR;
   int* fails = P.sticky + SY_FAILS;
@@ -1080,7 +1091,7 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
       }
     }
     seal_put();
-    signal(mygrp);
+    signal(mysig);
     ++L;
   };
   // ---- reset prologue: this launch zeroes its own counter block (and the granule tags), so no
@@ -1098,8 +1109,9 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
     __syncthreads();
     const bool ok0 = arrive_wait(a0, target, tmo, flag);
     if (ok0) {
-      if (tid < 4 && kCtrInts > 4 * (int)blockIdx.x + tid)
-        __hip_atomic_store(P.ctr + 4 * blockIdx.x + tid, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      constexpr int kRst = kOneWord ? 4 : kResetInts, kRstN = kOneWord ? kCtrOneInts : kCtrInts;
+      if (tid < kRst && kRstN > kRst * (int)blockIdx.x + tid)
+        __hip_atomic_store(P.ctr + kRst * blockIdx.x + tid, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (tid < 4) __hip_atomic_store(P.seal + 4 * blockIdx.x + tid, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (gran && tid < 32) {  // 512 B of the 128 KB granule block per workgroup
         const __amdgpu_buffer_rsrc_t rq = rsrc(P.gnp, kGroups * kH * 16);
@@ -1200,7 +1212,7 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
     float binv[2][4];  // epilogue vectors of the lane's columns (transposed layout), before the wait
     ld_cols(binv, P.bin + col0, q);
     PST(step);
-    if (!wait_ge(errw, fails, tmo, mygrp, 0, 1, 32 * L, flag) || !seal_wait(g, 1)) { fail_exit(); return; }
+    if (!wait_ge<!kOneWord>(errw, fails, tmo, mygrp, gws, gwn, gtarget(L), flag) || !seal_wait(g, 1)) { fail_exit(); return; }
     PST(step);
     f32x4 accm[NTW][2];  // every tile's products (several chunks: one streamed pass, epilogues after it)
     if constexpr (KH) gemm_kh<kC>(P.xs, r0, nr, (smem + wb * kWPanel), accm[0], wave, lane, PSTP(step), g, frag);
@@ -1224,9 +1236,9 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
     seal_put();
     if (dmafirst) {
       next_w(P.blk[0].w2);
-      signal_dma<16>(mygrp);
+      signal_dma<16>(mysig);
     } else {
-      signal(mygrp);
+      signal(mysig);
       next_w(P.blk[0].w2);
     }
     PST(step);
@@ -1301,7 +1313,7 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
         gbv = bw.gnb[col0 + tid];
       }
       PST(step);
-      if (!wait_ge(errw, fails, tmo, grp, 16, kGroups, 32 * L, flag) || !seal_wait(0, kGroups)) { fail_exit(); return; }  // every group: the halo rows of the neighbours
+      if (!wait_ge<!kOneWord>(errw, fails, tmo, grp, aws, awn, gtarget(L), flag) || !seal_wait(0, kGroups)) { fail_exit(); return; }  // every group: the halo rows of the neighbours
       PST(step);
       // va = w (1 + sc), vb = b (1 + sc) + sh (vab's arithmetic; w = 1, b = 0 without the affine)
       float hva[4], hvb[4], ova[2][4], ovb[2][4];
@@ -1534,7 +1546,7 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
         }
       }
       seal_put();
-      signal(mygrp);
+      signal(mysig);
       PST(step);
       ++L;
 
@@ -1542,7 +1554,7 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
       float b2v[2][4];  // epilogue vectors before the wait
       ld_cols(b2v, bw.b2 + col0, q);
       PST(step);
-      if (!wait_ge(errw, fails, tmo, mygrp, 0, 1, 32 * L, flag) || !seal_wait(g, 1)) { fail_exit(); return; }
+      if (!wait_ge<!kOneWord>(errw, fails, tmo, mygrp, gws, gwn, gtarget(L), flag) || !seal_wait(g, 1)) { fail_exit(); return; }
       PST(step);
       f32x4 accm_c2[NTW][2];  // every tile's products (several chunks: one streamed pass, epilogues after it)
       if constexpr (KH) gemm_kh<kH>(P.a2, r0, nr, (smem + wb * kWPanel), accm_c2[0], wave, lane, PSTP(step), g, frag);
@@ -1565,7 +1577,7 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
       seal_put();
       if (dmafirst) {
         next_w(bw.w3);
-        signal_dma<16>(mygrp);
+        signal_dma<16>(mysig);
       } else {
 #ifdef FL_STAMPS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1573,7 +1585,7 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
         __syncthreads();
         PST(step);  // every wave's
 #endif
-        signal(mygrp);
+        signal(mysig);
         next_w(bw.w3);
       }
       PST(step);
@@ -1590,7 +1602,7 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
       if (fin) fill_cols(alw, 1.0f);
       else ld_cols(alw, bw.lnmw + col0, q);
       PST(step);
-      if (!wait_ge(errw, fails, tmo, mygrp, 0, 1, 32 * L, flag) || !seal_wait(g, 1)) { fail_exit(); return; }
+      if (!wait_ge<!kOneWord>(errw, fails, tmo, mygrp, gws, gwn, gtarget(L), flag) || !seal_wait(g, 1)) { fail_exit(); return; }
       PST(step);
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt)
@@ -1627,9 +1639,9 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
       if (dmafirst) {
         if (fin) issue_out();  // conv_out's panel (into the other buffer; the flip follows the loop)
         else next_w(bw.m0);
-        signal_dma<16>(mygrp);
+        signal_dma<16>(mysig);
       } else {
-        signal(mygrp);
+        signal(mysig);
         if (fin) issue_out();
         else next_w(bw.m0);
       }
@@ -1643,7 +1655,7 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
       ld_cols(fa0, fo0 + col0, q);
       ld_cols(fb0, fo0 + H + col0, q);
       PST(step);
-      if (!wait_ge(errw, fails, tmo, mygrp, 0, 1, 32 * L, flag) || !seal_wait(g, 1)) { fail_exit(); return; }
+      if (!wait_ge<!kOneWord>(errw, fails, tmo, mygrp, gws, gwn, gtarget(L), flag) || !seal_wait(g, 1)) { fail_exit(); return; }
       PST(step);
       // the epilogue's row statistics of x (conv_3's partials).  One chunk: only their loads go out here, ahead of the
       // A loads; the combine follows the MFMA loop, which does not need it (load_row_partials).  Several chunks: the
@@ -1682,9 +1694,9 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
       seal_put();
       if (dmafirst) {
         next_w(bw.m2);
-        signal_dma<16>(mygrp);
+        signal_dma<16>(mysig);
       } else {
-        signal(mygrp);
+        signal(mysig);
         next_w(bw.m2);
       }
       PST(step);
@@ -1695,7 +1707,7 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
       ld_cols(g2v, mb + 5 * H + col0, q);
       ld_cols(bm2, bw.mb2 + col0, q);
       PST(step);
-      if (!wait_ge(errw, fails, tmo, mygrp, 0, 1, 32 * L, flag) || !seal_wait(g, 1)) { fail_exit(); return; }
+      if (!wait_ge<!kOneWord>(errw, fails, tmo, mygrp, gws, gwn, gtarget(L), flag) || !seal_wait(g, 1)) { fail_exit(); return; }
       PST(step);
       f32x4 accm_m2[NTW][2];  // every tile's products (several chunks: one streamed pass, epilogues after it)
       if constexpr (KH) gemm_kh<kH>(P.u, r0, nr, (smem + wb * kWPanel), accm_m2[0], wave, lane, PSTP(step), g, frag);
@@ -1718,9 +1730,9 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
       seal_put();
       if (dmafirst) {
         next_w(P.blk[blk + 1].w2);
-        signal_dma<16>(mygrp);
+        signal_dma<16>(mysig);
       } else {
-        signal(mygrp);
+        signal(mysig);
         next_w(P.blk[blk + 1].w2);
       }
       PST(step);
@@ -1743,7 +1755,7 @@ __global__ __launch_bounds__(kThreads, 1) void den_persist_kernel(Params P) {
       }
     }
     PST(step);
-    if (!wait_ge(errw, fails, tmo, mygrp, 0, 1, 32 * L, flag) || !seal_wait(g, 1)) { fail_exit(); return; }
+    if (!wait_ge<!kOneWord>(errw, fails, tmo, mygrp, gws, gwn, gtarget(L), flag) || !seal_wait(g, 1)) { fail_exit(); return; }
     PST(step);
     [[maybe_unused]] u32x4 rp_out[8];  // row statistics as in mlp.0: loads here, the combine after the MFMA loop
     if constexpr (kDefer) load_row_partials(rp_out, P.xpart[1], TT, r0, nr, wave, lane, g, tm);
@@ -2046,6 +2058,21 @@ extern "C" FLAMED_API int flamed_persist_rowpart(int B, int T, const int* lens, 
   row_owner(*row - u * T, Lu, gpu, opt, gi, ol);
   *owner_g = u * gpu + gi;
   *owner_lrow = ol;
+  return fl::kOk;
+}
+
+// Host-side view of the counter block (include/flamed_diag.h; CPU unit test).
+extern "C" FLAMED_API int flamed_persist_ctr_layout(int opt, int g, int s, int L, int* img, int* gn, int* err, int* ctr_ints,
+                                                    int* reset_ints) {
+  using namespace fl::pk;
+  if (!img || !gn || !err || !ctr_ints || !reset_ints || g < 0 || g >= kGroups || s < 0 || s >= kSlots) return fl::kBadArg;
+  const ArriveImage a = arrive_image(opt, g, s);
+  const int v[7] = {a.sig, a.base, a.stride(), a.n(), a.abase(), a.an(), a.target(L)};
+  for (int i = 0; i < 7; ++i) img[i] = v[i];
+  *gn = CT_GN + 16 * s;
+  *err = CT_ERR;
+  *ctr_ints = a.sh ? kCtrInts : kCtrOneInts;  // what a launch under this image touches and zeroes
+  *reset_ints = kWGs * (a.sh ? kResetInts : 4);
   return fl::kOk;
 }
 

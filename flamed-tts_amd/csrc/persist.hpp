@@ -23,7 +23,9 @@
 // halo rows) is stored write-through (sc1), drained by every storing
 // wave, then one lane adds to a counter; consumers poll with sc1 loads and read the data with sc1
 // loads only (cdna_hip_programming.md §6 Guideline 16, table row 1: no release / acquire fences).
-//   group counters  grp[g]: the 32 slots of g add 1 after each group phase (GEMM operands, partials)
+//   group counters  after each group phase (GEMM operands, partials) each of the 32 slots of g adds 1 to its shard's
+//                           word: four words per group, eight adds each per hand-off (one word and 32 adds under
+//                           persist_opt kOptOneWord and in the variants of one_word_variant; "counters" below)
 //   GroupNorm       gn[s]:  the 8 groups' slot-s workgroups add 1 after publishing their partials (the counter form,
 //                           persist_opt without 512)
 // Two exchanges need no drain and no counter: their data is the flag.  Each value travels as an 8-byte {tag, fp32}
@@ -69,8 +71,53 @@ constexpr int L_GNV = L_RED + 8 * kCols * 4;
 constexpr int L_FLAG = L_GNV + kCols * 16;
 constexpr int kLds = (L_FLAG + 16 + 15) / 16 * 16;
 static_assert(kLds <= 160 * 1024, "persistent solve LDS");
-// counters (ints, one 64-B line each); zeroed by the launch itself (its reset prologue)
-constexpr int CT_GRP = 0, CT_GN = 16 * kGroups, CT_ERR = CT_GN + 16 * kSlots, kCtrInts = CT_ERR + 16;
+// counters (ints); zeroed by the launch itself (its reset prologue)
+//   [CT_GRP, CT_GN)   one word per row group, 64 B apart: the one-word image (32 adds per hand-off)
+//   [CT_GN, CT_ERR)   GroupNorm, one word per slot, 64 B apart
+//   CT_ERR            the error word, alone on its 128-B line        -- up to here the block every variant has had
+//   [CT_SHD, kCtrInts) group arrivals, sharded: kShards words per row group, each on a 128-B line of its own.  Shard k
+//                     takes the arrivals of slots 8 k .. 8 k + 7 (under the 2 x 4 XCD grid the group's eight workgroups
+//                     on one XCD; under the other placements the same fixed partition), so a word sees 8 adds per
+//                     hand-off instead of 32 and a consumer polls 4 words (the depthwise phase: all 32), each up to
+//                     8 x the hand-off number
+// A sharded variant zeroes all kCtrInts words (kResetInts per workgroup); a one-word variant only ever touches the
+// first kCtrOneInts and zeroes those, 4 per workgroup, as before.
+constexpr int kLineInts = 32, kShards = 4, kShardSlots = kSlots / kShards;
+constexpr int CT_GRP = 0, CT_GN = 16 * kGroups, CT_ERR = CT_GN + 16 * kSlots, kCtrOneInts = CT_ERR + 16;
+constexpr int CT_SHD = (kCtrOneInts + kLineInts - 1) / kLineInts * kLineInts;
+constexpr int kCtrInts = CT_SHD + kGroups * kShards * kLineInts, kResetInts = 8;
+static_assert(kCtrInts <= kWGs * kResetInts && kCtrOneInts <= kWGs * 4, "the reset prologue covers the block");
+static_assert(CT_GN % kLineInts == 0 && CT_ERR % kLineInts == 0 && CT_ERR + kLineInts <= CT_SHD,
+              "group words, GroupNorm words and the error word share no line");
+constexpr int kOptOneWord = 1 << 22;
+// Kernel variants <KH, NTW, RK2, RAG> that keep the one-word image at compile time (persist_opt kOptOneWord has nothing
+// to select there): for them the hand-off code is the single-word code unchanged, registers and scratch included.  They
+// are the variants whose sharded build needed more scratch than the single-word one
+// (profiles/arrive_shard_resources.txt), the five-chunk Euler variant among them, which also measured slower sharded.
+__host__ __device__ constexpr bool one_word_variant(bool KH, int NTW, bool RK2, bool RAG) {
+  if (KH) return false;
+  if (!RAG) return !RK2 ? (NTW == 4 || NTW == 5) : (NTW == 5 || NTW == 8);
+  return !RK2 ? ((NTW >= 3 && NTW <= 5) || NTW == 7) : (NTW <= 3 || NTW == 5);
+}
+// Group hand-off image of a workgroup (group g, slot s) under persist_opt `opt`, worked out once before the step loop
+// (host-callable for the CPU unit test, flamed_persist_ctr_layout): the word it signals (`sig`), the first word a wait
+// for group g polls (`base`), and `sh`, from which the rest follows by shifts -- a group wait polls 1 << sh words, the
+// all-group wait kGroups << sh from abase(), `stride()` ints apart, and every polled word must reach
+// (kSlots x the hand-off number) >> sh.  sh = 2: the four shard words; sh = 0: the one word.
+struct ArriveImage {
+  int sig, base, sh;
+  __host__ __device__ int n() const { return 1 << sh; }
+  __host__ __device__ int an() const { return kGroups << sh; }
+  __host__ __device__ int abase() const { return sh ? CT_SHD : CT_GRP; }
+  __host__ __device__ int stride() const { return 16 << (sh >> 1); }
+  __host__ __device__ int target(int L) const { return (kSlots * L) >> sh; }
+};
+static_assert((1 << 2) == kShards && (16 << 1) == kLineInts && (kSlots >> 2) == kShardSlots, "ArriveImage shifts");
+__host__ __device__ inline ArriveImage arrive_image(int opt, int g, int s) {
+  if (opt & kOptOneWord) return {CT_GRP + 16 * g, CT_GRP + 16 * g, 0};
+  const int w = CT_SHD + g * kShards * kLineInts;
+  return {w + (s / kShardSlots) * kLineInts, w, 2};
+}
 // sticky words (never reset; zeroed once at allocation): failed launches, and the two monotonic arrival
 // counters of the reset prologue, each on a 128-B line of its own
 constexpr int SY_FAILS = 0, SY_ARRIVE0 = 32, SY_ARRIVE1 = 64, SY_PFAIL = 96, kStickyInts = 128;

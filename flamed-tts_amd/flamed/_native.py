@@ -127,6 +127,7 @@ HIP_DIAG_SIGNATURES = {
     "flamed_den_ws_offsets": (c_int, [P, c_int, c_int, ctypes.POINTER(c_size_t)]),
     "flamed_vq_ws_offsets": (c_int, [P, c_int, c_int, ctypes.POINTER(c_size_t)]),
     "flamed_persist_ticket": (c_int, [ctypes.c_uint, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(c_int)]),
+    "flamed_persist_ctr_layout": (c_int, [c_int, c_int, c_int, c_int] + [ctypes.POINTER(c_int)] * 5),
     "flamed_persist_rowpart": (c_int, [c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_int, c_int, ctypes.POINTER(c_int),
                                        ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "flamed_den_chain_info": (c_int, [P, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),

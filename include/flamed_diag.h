@@ -78,6 +78,13 @@ FLAMED_API int flamed_vq_ws_offsets(flamed_vq_t h, int B, int T, size_t* off);
  * completes the launch of `ticket` (a fetch_add result), and whether counter value `cur` has reached it
  * (wrap-safe across 2^32). */
 FLAMED_API int flamed_persist_ticket(unsigned ticket, unsigned cur, unsigned* target, int* reached);
+/* The persistent solve's counter block, host-side (no GPU), in ints from its start: for workgroup (group g < 8,
+ * slot s < 32) under persist_opt `opt` and hand-off number L, img[7] = {the word it signals, the first word of a wait for group g, the
+ * stride between polled words, how many a group wait polls, the first word and the count of the all-group wait, what
+ * each polled word must reach at hand-off L}; `*gn` the GroupNorm counter of slot s, `*err` the error word,
+ * `*ctr_ints` how many words a launch under this image touches and `*reset_ints` how many its reset prologue (256
+ * workgroups) zeroes. */
+FLAMED_API int flamed_persist_ctr_layout(int opt, int g, int s, int L, int* img, int* gn, int* err, int* ctr_ints, int* reset_ints);
 /* The persistent solve's tile-major LayerNorm row partials, host-side (no GPU): for B utterances of T frames (lens:
  * B exact lengths, or NULL), row partition `opt` (persist_opt; bit 2), group g < 8, row lrow of that group and slot
  * s < 32: the frame `*row` (row index in the B x T batch) and the byte offset `*off` of its (mean, M2) cell in the
