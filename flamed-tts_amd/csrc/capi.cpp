@@ -87,6 +87,7 @@ int tune_apply(Tune& t, const char* key, int value) {
       {"pva_split", &Tune::pva_split, 0, 1, nullptr},
       {"persist", &Tune::persist, 0, 1, nullptr},
       {"split_batch", &Tune::split_batch, 1, 4, nullptr},
+      {"ragged_launch", &Tune::ragged_launch, 0, 1, nullptr},
       {"split_graph", &Tune::split_graph, 0, 1, nullptr},
       {"split_prio", &Tune::split_prio, 0, 2, nullptr},
       {"prio_all", &Tune::prio_all, 0, 1, nullptr},

@@ -175,6 +175,7 @@ struct Tune {
   int fuse_euler = 1;      // small-M solve graphs: conv_out combine + Euler update inside the next proj_in
   int persist = 1;         // B = 1 bf16 solves: one persistent launch for all steps (persist.hpp)
   int split_batch = 2;     // large-M bf16 solves: sub-batch chains as parallel graph branches (den_split)
+  int ragged_launch = 1;   // exact lengths behind the persistent launch: the ragged batch on the launch path (0: one utterance after another)
   int split_graph = 0;     // split chains: 0 one graph per chain on its own (priority) stream, 1 one graph with branches
   int prio_all = 0;       // experiment: every graph-path solve replays on the handle's chain-0 stream of split_prio
   int split_prio = 2;      // split chains' replay streams (den_chain_streams): 0 caller + highest, 1 all low, 2 all high

@@ -17,6 +17,8 @@
 #include "gemm_dma.hpp"
 #include "gemm_8p.hpp"
 #include "graph.hpp"
+#include "lens.hpp"
+#include "seqend.hpp"
 #include "persist.hpp"
 
 #include <mutex>
@@ -591,13 +593,16 @@ constexpr int kDwCG = 64, kDwTC = 64;
 // the workgroups, half the halo re-read; measured slower at B = 64, 97 vs 82 us per launch,
 // profiles/r01_b64_bigpath.txt).  Below tn().dw_cg32_rows rows: narrow tn().dw_cg_small-channel groups.
 
-template <bool AFF, int KS, int TC, int CG = kDwCG, typename XT = float>  // XT: X and D type (bf16 on the x16 path)
+// End (seqend.hpp): where utterance b ends.  Exact lengths: rows from Te = len_b on are staged as zeros (a select: they
+// may hold anything), counted in no statistic and not stored; the batch stride stays T, and a workgroup whose chunk
+// lies wholly behind Te still publishes its (count 0) partial and takes its ticket.
+template <bool AFF, int KS, int TC, int CG = kDwCG, typename XT = float, class End = SeqEnd<false>>  // XT: X and D type (bf16 on the x16 path)
 __global__ __launch_bounds__(256) void dwconv_stats_kernel(const XT* __restrict__ X, int H, const float* __restrict__ S,
                                                            int NT, int tw, float eps_ln, ModRef mod,
                                                            const float* __restrict__ lnw, const float* __restrict__ lnb,
                                                            const float* __restrict__ dww, const float* __restrict__ dwb,
                                                            XT* __restrict__ D, float* __restrict__ GP, int T, int TS,
-                                                           int* __restrict__ gcnt, float* __restrict__ GNS) {
+                                                           int* __restrict__ gcnt, float* __restrict__ GNS, End end) {
   constexpr int HALO = KS / 2, SR = TC + 2 * HALO, RG = 256 / CG, RPT = TC / RG, WIN = RPT + KS - 1;
   constexpr int C4 = CG / 4;                      // float4 chunks per staged row
   constexpr int NX = (SR * C4 + 255) / 256;          // float4 loads per thread for the X tile
@@ -610,6 +615,8 @@ __global__ __launch_bounds__(256) void dwconv_stats_kernel(const XT* __restrict_
   const int c0 = blockIdx.x * CG, ts = blockIdx.y, b = blockIdx.z;
   const int t0 = ts * TC;
   const int cl = tid % CG, rg = tid / CG, c = c0 + cl;
+  int Te = T;  // the utterance's own end
+  if constexpr (End::kExact) Te = end.end(b, T);
   mod = mod.at();
   // every independent global load is issued up front: X tile (float4), conv taps, LN stats, alpha/beta
   float4 xv[NX];
@@ -618,7 +625,7 @@ __global__ __launch_bounds__(256) void dwconv_stats_kernel(const XT* __restrict_
     const int q = tid + j * 256;
     const int r = q / C4, c4 = q - r * C4;
     const int t = t0 - HALO + r;
-    xv[j] = (q < SR * C4 && t >= 0 && t < T) ? ldx4<XT>(X + ((size_t)b * T + t) * H + c0 + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    xv[j] = (q < SR * C4 && t >= 0 && t < Te) ? ldx4<XT>(X + ((size_t)b * T + t) * H + c0 + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
   }
   float w[KS];
 #pragma unroll
@@ -635,7 +642,7 @@ __global__ __launch_bounds__(256) void dwconv_stats_kernel(const XT* __restrict_
   }
   if (tid < SR) {
     int t = t0 - HALO + tid;
-    if (t >= 0 && t < T) row_stats_from_partials(S, b * T + t, NT, tw, eps_ln, rs[2 * tid], rs[2 * tid + 1]);
+    if (t >= 0 && t < Te) row_stats_from_partials(S, b * T + t, NT, tw, eps_ln, rs[2 * tid], rs[2 * tid + 1]);
   }
   __syncthreads();
   FL_STAMP(1);
@@ -646,7 +653,7 @@ __global__ __launch_bounds__(256) void dwconv_stats_kernel(const XT* __restrict_
     const int r = q / C4, c4 = q - r * C4;
     const int t = t0 - HALO + r;
     float o[4] = {0.f, 0.f, 0.f, 0.f};
-    if (t >= 0 && t < T) {
+    if (t >= 0 && t < Te) {
       const float xs[4] = {xv[j].x, xv[j].y, xv[j].z, xv[j].w};
       const float mean = rs[2 * r], rstd = rs[2 * r + 1];
 #pragma unroll
@@ -679,7 +686,7 @@ __global__ __launch_bounds__(256) void dwconv_stats_kernel(const XT* __restrict_
 #pragma unroll
     for (int j = 0; j < KS; ++j) a += w[j] * win[q + j];
     vals[q] = a;
-    if (t0 + rg * RPT + q < T) {
+    if (t0 + rg * RPT + q < Te) {
       cn += 1.f;
       cs += a;
     }
@@ -690,13 +697,13 @@ __global__ __launch_bounds__(256) void dwconv_stats_kernel(const XT* __restrict_
 #pragma unroll
     for (int q = 0; q < RPT; ++q) {
       const int t = t0 + rg * RPT + q;
-      if (t < T) store_val<XT>(D + ((size_t)b * T + t) * H + c, vals[q]);
+      if (t < Te) store_val<XT>(D + ((size_t)b * T + t) * H + c, vals[q]);
     }
   };
   float cm = cn > 0.f ? cs / cn : 0.f, c2 = 0.f;
 #pragma unroll
   for (int q = 0; q < RPT; ++q)
-    if (t0 + rg * RPT + q < T) {
+    if (t0 + rg * RPT + q < Te) {
       float d = vals[q] - cm;
       c2 += d * d;
     }
@@ -756,12 +763,13 @@ __global__ __launch_bounds__(256) void dwconv_stats_kernel(const XT* __restrict_
       if (t0c + i < TS) chan_combine(n, mu, m2, q[i][0], q[i][1], q[i][2]);
   }
   GNS[((size_t)b * H + c0 + tid) * 2] = mu;
-  GNS[((size_t)b * H + c0 + tid) * 2 + 1] = 1.0f / sqrtf(m2 / (float)T + 1e-5f);
+  GNS[((size_t)b * H + c0 + tid) * 2 + 1] = 1.0f / sqrtf(m2 / (float)Te + 1e-5f);
   FL_STAMP(5);
 }
 
 // GroupNorm(H,H) statistics over all T frames of each (utterance, channel): GNS[b][c] = (mean, rstd).
-__global__ void gn_finalize_kernel(const float* __restrict__ GP, float* __restrict__ GNS, int H, int T, int TS, float eps) {
+template <class End = SeqEnd<false>>
+__global__ void gn_finalize_kernel(const float* __restrict__ GP, float* __restrict__ GNS, int H, int T, int TS, float eps, End end) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   int b = blockIdx.y;
   if (c >= H) return;
@@ -778,16 +786,16 @@ __global__ void gn_finalize_kernel(const float* __restrict__ GP, float* __restri
       if (t0 + i < TS) chan_combine(n, mu, m2, q[i][0], q[i][1], q[i][2]);
   }
   GNS[((size_t)b * H + c) * 2] = mu;
-  GNS[((size_t)b * H + c) * 2 + 1] = 1.0f / sqrtf(m2 / (float)T + eps);
+  GNS[((size_t)b * H + c) * 2 + 1] = 1.0f / sqrtf(m2 / (float)end.end(b, T) + eps);
 }
 
-template <bool AFF, typename XT = float>
+template <bool AFF, typename XT = float, class End = SeqEnd<false>>
 // part 1: conv + partials (+ GroupNorm finalize fused in when gcnt is given); part 2: standalone
 // finalize (used only without counters).  XT: type of X and D (bf16 on the large-M x16 path, which
 // always uses the 64-channel workgroups).
 static int launch_dwconv_stats(const XT* X, int H, const float* S, int NT, int tw, ModRef mod, const float* lnw,
                                const float* lnb, const float* dww, const float* dwb, XT* D, float* GP, float* GNS,
-                               int B, int T, hipStream_t st, int part, int* gcnt) {
+                               int B, int T, hipStream_t st, int part, int* gcnt, End end = End()) {
   FL_REQUIRE(H % kDwCG == 0 && H % 256 == 0, "dwconv: H=%d must be a multiple of 256", H);
   const int TC = ((size_t)B * T >= 8192 && tn().dw_tc_big == 128) ? 128 : kDwTC;
   const int TS = (T + TC - 1) / TC;
@@ -795,21 +803,21 @@ static int launch_dwconv_stats(const XT* X, int H, const float* S, int NT, int t
   const bool cg32 = std::is_same<XT, float>::value && (size_t)B * T < (size_t)tn().dw_cg32_rows;
   if (part != 2) {
     if (TC == 128)
-      hipLaunchKernelGGL((dwconv_stats_kernel<AFF, 31, 128, kDwCG, XT>), dim3(H / kDwCG, TS, B), dim3(256), 0, st, X, H, S, NT, tw,
-                         1e-6f, mod, lnw, lnb, dww, dwb, D, GP, T, TS, gcnt, GNS);
+      hipLaunchKernelGGL((dwconv_stats_kernel<AFF, 31, 128, kDwCG, XT, End>), dim3(H / kDwCG, TS, B), dim3(256), 0, st, X, H, S, NT, tw,
+                         1e-6f, mod, lnw, lnb, dww, dwb, D, GP, T, TS, gcnt, GNS, end);
     else if (cg32 && tn().dw_cg_small == 16)
-      hipLaunchKernelGGL((dwconv_stats_kernel<AFF, 31, kDwTC, 16, XT>), dim3(H / 16, TS, B), dim3(256), 0, st, X, H, S, NT, tw,
-                         1e-6f, mod, lnw, lnb, dww, dwb, D, GP, T, TS, gcnt, GNS);
+      hipLaunchKernelGGL((dwconv_stats_kernel<AFF, 31, kDwTC, 16, XT, End>), dim3(H / 16, TS, B), dim3(256), 0, st, X, H, S, NT, tw,
+                         1e-6f, mod, lnw, lnb, dww, dwb, D, GP, T, TS, gcnt, GNS, end);
     else if (cg32)
-      hipLaunchKernelGGL((dwconv_stats_kernel<AFF, 31, kDwTC, 32, XT>), dim3(H / 32, TS, B), dim3(256), 0, st, X, H, S, NT, tw,
-                         1e-6f, mod, lnw, lnb, dww, dwb, D, GP, T, TS, gcnt, GNS);
+      hipLaunchKernelGGL((dwconv_stats_kernel<AFF, 31, kDwTC, 32, XT, End>), dim3(H / 32, TS, B), dim3(256), 0, st, X, H, S, NT, tw,
+                         1e-6f, mod, lnw, lnb, dww, dwb, D, GP, T, TS, gcnt, GNS, end);
     else
-      hipLaunchKernelGGL((dwconv_stats_kernel<AFF, 31, kDwTC, kDwCG, XT>), dim3(H / kDwCG, TS, B), dim3(256), 0, st, X, H, S, NT,
-                         tw, 1e-6f, mod, lnw, lnb, dww, dwb, D, GP, T, TS, gcnt, GNS);
+      hipLaunchKernelGGL((dwconv_stats_kernel<AFF, 31, kDwTC, kDwCG, XT, End>), dim3(H / kDwCG, TS, B), dim3(256), 0, st, X, H, S, NT,
+                         tw, 1e-6f, mod, lnw, lnb, dww, dwb, D, GP, T, TS, gcnt, GNS, end);
     FL_LAUNCH_CHECK();
   }
   if (part != 1 && !gcnt) {
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3(H / 256, B), dim3(256), 0, st, GP, GNS, H, T, TS, 1e-5f);
+    hipLaunchKernelGGL(gn_finalize_kernel<End>, dim3(H / 256, B), dim3(256), 0, st, GP, GNS, H, T, TS, 1e-5f, end);
     FL_LAUNCH_CHECK();
   }
   return kOk;
@@ -877,12 +885,15 @@ __device__ __forceinline__ dg_f2 dg_add1(dg_f2 a, dg_f2 b) {  // scalar pair add
   asm volatile("" : "+v"(x), "+v"(y));
   return dg_f2{x, y};
 }
-template <bool AFF, int NCH, typename XT, int VAR = 1>
+// End: the utterance's own end Te replaces T in every bound, count and divisor (chunk loop, clamp, staging, statistics,
+// stores); addresses keep the stride T.  A thread whose frames all lie behind Te still convolves chunk 0's zero rows, so
+// its K is finite.
+template <bool AFF, int NCH, typename XT, class End = SeqEnd<false>, int VAR = 1>
 __global__ __launch_bounds__(256) void dwgn_kernel(const XT* __restrict__ X, int H, const float* __restrict__ S, int NT, int tw,
                                                    float eps_ln, ModRef mod, const float* __restrict__ lnw,
                                                    const float* __restrict__ lnb, const float* __restrict__ dww,
                                                    const float* __restrict__ dwb, const float* __restrict__ gnw,
-                                                   const float* __restrict__ gnb, bf16* __restrict__ A, int T) {
+                                                   const float* __restrict__ gnb, bf16* __restrict__ A, int T, End end) {
   constexpr int KS = 31, HALO = KS / 2, CG = 32, NP = CG / 2, TC = 64, SR = TC + 2 * HALO, RG = 16, RPT = TC / RG;
   constexpr int WIN = RPT + KS - 1, LDH = CG + 8;  // padded LDS row
   constexpr int NTH = 256, C4 = CG / 4, NX = (SR * C4 + NTH - 1) / NTH;
@@ -893,7 +904,8 @@ __global__ __launch_bounds__(256) void dwgn_kernel(const XT* __restrict__ X, int
   const int tid = threadIdx.x;
   const int c0 = blockIdx.x * CG, b = blockIdx.y;
   const int pp = tid % NP, rg = tid / NP, c = c0 + 2 * pp;  // channels c, c + 1
-  const int nch = (T + TC - 1) / TC;
+  const int Te = end.end(b, T);
+  const int nch = (Te + TC - 1) / TC;
   mod = mod.at();
   // tiles of chunks ch and ch + 1 in flight, held RAW (bf16 pairs or fp32): converting at load time
   // would make the compiler wait for each prefetch right after issuing it
@@ -914,13 +926,13 @@ __global__ __launch_bounds__(256) void dwgn_kernel(const XT* __restrict__ X, int
       const int t = t0 - HALO + r;
       // unconditional load from a clamped row (rows outside the utterance are zeroed when staged): no
       // branches around the loads, so the wait before staging chunk ch leaves chunk ch + 1's in flight
-      const int tc = min(max(t, 0), T - 1), c4c = q < SR * C4 ? c4 : 0;
+      const int tc = min(max(t, 0), Te - 1), c4c = q < SR * C4 ? c4 : 0;
       xs[j] = *reinterpret_cast<const XR*>(X + ((size_t)b * T + tc) * H + c0 + 4 * c4c);
     }
   };
   load_x(xv[0], 0);
   load_x(xv[1], min(TC, (nch - 1) * TC));
-  for (int t = tid; t < T; t += NTH) row_stats_from_partials(S, b * T + t, NT, tw, eps_ln, rs[2 * t], rs[2 * t + 1]);
+  for (int t = tid; t < Te; t += NTH) row_stats_from_partials(S, b * T + t, NT, tw, eps_ln, rs[2 * t], rs[2 * t + 1]);
   dg_f2 w[KS];
 #pragma unroll
   for (int j = 0; j < KS; ++j) w[j] = *reinterpret_cast<const dg_f2*>(dww + (size_t)j * H + c);  // tap-major (KS, H) copy
@@ -951,7 +963,7 @@ __global__ __launch_bounds__(256) void dwgn_kernel(const XT* __restrict__ X, int
         const int t = t0 - HALO + r;
         dg_f2 lo = {0.f, 0.f}, hi = {0.f, 0.f};
         const float4 xcj = cvt(xr[j]);
-        if (t >= 0 && t < T) {
+        if (t >= 0 && t < Te) {
           const dg_f2 mean = rs[2 * t], rstd = rs[2 * t + 1];
           const float4 a4 = *reinterpret_cast<const float4*>(va + 4 * c4), b4 = *reinterpret_cast<const float4*>(vb + 4 * c4);
           lo = dg_lnmod<VAR>(dg_f2{xcj.x, xcj.y}, mean, rstd, dg_f2{a4.x, a4.y}, dg_f2{b4.x, b4.y});
@@ -987,7 +999,7 @@ __global__ __launch_bounds__(256) void dwgn_kernel(const XT* __restrict__ X, int
       for (int q = 0; q < RPT; ++q)
         if (r - q >= 0 && r - q < KS) acc[q] = dg_fma<VAR>(w[r - q], row, acc[q]);
     }
-    const int nv = T - (t0 + rg * RPT);  // valid frames of this thread in the chunk (may be <= 0)
+    const int nv = Te - (t0 + rg * RPT);  // valid frames of this thread in the chunk (may be <= 0)
 #pragma unroll
     for (int q = 0; q < RPT; ++q) {
       const dg_f2 a = acc[q];
@@ -1003,7 +1015,7 @@ __global__ __launch_bounds__(256) void dwgn_kernel(const XT* __restrict__ X, int
   {
     int n = 0;  // frames this thread covered
 #pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) n += max(0, min(RPT, T - (ch * TC + rg * RPT)));
+    for (int ch = 0; ch < NCH; ++ch) n += max(0, min(RPT, Te - (ch * TC + rg * RPT)));
     const float fn = (float)n, inv = n > 0 ? 1.0f / fn : 0.f;
     const dg_f2 m = K + s1 * inv, m2 = s2 - s1 * s1 * inv;
     red[(rg * CG + 2 * pp) * 3 + 0] = fn;
@@ -1019,7 +1031,7 @@ __global__ __launch_bounds__(256) void dwgn_kernel(const XT* __restrict__ X, int
 #pragma unroll
     for (int g = 0; g < RG; ++g) chan_combine(n, m, m2, red[(g * CG + tid) * 3], red[(g * CG + tid) * 3 + 1], red[(g * CG + tid) * 3 + 2]);
     gmu[tid] = m;
-    gsc[tid] = (1.0f / sqrtf(m2 / (float)T + 1e-5f)) * gnw[c0 + tid];
+    gsc[tid] = (1.0f / sqrtf(m2 / (float)Te + 1e-5f)) * gnw[c0 + tid];
   }
   __syncthreads();
   const dg_f2 mu = {gmu[2 * pp], gmu[2 * pp + 1]}, sc = {gsc[2 * pp], gsc[2 * pp + 1]};
@@ -1038,18 +1050,18 @@ __global__ __launch_bounds__(256) void dwgn_kernel(const XT* __restrict__ X, int
   for (int ch = 0; ch < NCH; ++ch)
 #pragma unroll
     for (int q = 0; q < RPT; ++q)
-      if (ch * TC + rg * RPT + q < T) *reinterpret_cast<bf16x2*>(ap + (size_t)(ch * TC + q) * H) = ob[ch][q];
+      if (ch * TC + rg * RPT + q < Te) *reinterpret_cast<bf16x2*>(ap + (size_t)(ch * TC + q) * H) = ob[ch][q];
 }
 
-template <bool AFF, typename XT>
+template <bool AFF, typename XT, class End = SeqEnd<false>>
 static int launch_dwgn(const XT* X, int H, const float* S, int NT, int tw, ModRef mod, const float* lnw, const float* lnb,
                        const float* dww, const float* dwb, const float* gnw, const float* gnb, bf16* A, int B, int T,
-                       hipStream_t st) {
+                       hipStream_t st, End end = End()) {
   FL_REQUIRE(H % 32 == 0 && T >= 1 && T <= kDgMaxT && mod.div % T == 0, "dwgn: H=%d T=%d div=%d", H, T, mod.div);
   const int nch = (T + 63) / 64;
   const dim3 g(H / 32, B), blk(256);
-#define FL_DWGN(N) hipLaunchKernelGGL((dwgn_kernel<AFF, N, XT>), g, blk, 0, st, X, H, S, NT, tw, 1e-6f, mod, lnw, lnb, dww, dwb, gnw, gnb, A, T)
-#define FL_DWGN_V(N, V) hipLaunchKernelGGL((dwgn_kernel<AFF, N, XT, V>), g, blk, 0, st, X, H, S, NT, tw, 1e-6f, mod, lnw, lnb, dww, dwb, gnw, gnb, A, T)
+#define FL_DWGN(N) hipLaunchKernelGGL((dwgn_kernel<AFF, N, XT, End>), g, blk, 0, st, X, H, S, NT, tw, 1e-6f, mod, lnw, lnb, dww, dwb, gnw, gnb, A, T, end)
+#define FL_DWGN_V(N, V) hipLaunchKernelGGL((dwgn_kernel<AFF, N, XT, End, V>), g, blk, 0, st, X, H, S, NT, tw, 1e-6f, mod, lnw, lnb, dww, dwb, gnw, gnb, A, T, end)
   if (tn().dwgn_var == 0 && nch == 7) FL_DWGN_V(7, 0);
   else if (tn().dwgn_var == 2 && nch == 7) FL_DWGN_V(7, 2);
   else if (nch <= 2) FL_DWGN(2);
@@ -1074,12 +1086,13 @@ static int launch_dwgn(const XT* X, int H, const float* S, int NT, int tw, ModRe
 // + one LDS exchange each, fixed order), and the normalised bf16 conv_2 operand is written with
 // LoadGN's arithmetic (x - mean) * (rstd * gn_w) + gn_b.  conv_2 then runs as a plain bf16 GEMM on the
 // LDS-DMA loop.
-template <bool AFF, int RPT>
+// End: as in dwgn_kernel (Te for T in every clamp, bound, count and divisor; stride T in every address).
+template <bool AFF, int RPT, class End = SeqEnd<false>>
 __global__ __launch_bounds__(256) void dwgn_small_kernel(const float* __restrict__ X, int H, const float* __restrict__ S, int NT,
                                                          int tw, float eps_ln, ModRef mod, const float* __restrict__ lnw,
                                                          const float* __restrict__ lnb, const float* __restrict__ dww,
                                                          const float* __restrict__ dwb, const float* __restrict__ gnw,
-                                                         const float* __restrict__ gnb, bf16* __restrict__ A, int T) {
+                                                         const float* __restrict__ gnb, bf16* __restrict__ A, int T, End end) {
   constexpr int KS = 31, HALO = KS / 2, CG = 8, WIN = RPT + KS - 1, MAXR = 64 * RPT + 2 * HALO;
   static_assert(RPT % 2 == 1, "odd RPT keeps the window reads conflict-free");
   __shared__ float hs[MAXR * CG];
@@ -1087,6 +1100,7 @@ __global__ __launch_bounds__(256) void dwgn_small_kernel(const float* __restrict
   const int tid = threadIdx.x;
   const int c0 = blockIdx.x * CG, b = blockIdx.y;
   const int p = tid & 3, rg = tid >> 2, c = c0 + 2 * p;
+  const int Te = end.end(b, T);
   FL_STAMP(0);
   mod = mod.at();
   // this thread's staged rows r = tid, tid + 256, ... (frame r - HALO): X loads issued first (clamped
@@ -1095,7 +1109,7 @@ __global__ __launch_bounds__(256) void dwgn_small_kernel(const float* __restrict
   float4 xv[NSR][2];
 #pragma unroll
   for (int i = 0; i < NSR; ++i) {
-    const int t = min(max(tid + 256 * i - HALO, 0), T - 1);
+    const int t = min(max(tid + 256 * i - HALO, 0), Te - 1);
     const float* xr = X + ((size_t)b * T + t) * H + c0;
     xv[i][0] = ld4(xr);
     xv[i][1] = ld4(xr + 4);
@@ -1107,7 +1121,7 @@ __global__ __launch_bounds__(256) void dwgn_small_kernel(const float* __restrict
     float2 q[NSR][16];
 #pragma unroll
     for (int i = 0; i < NSR; ++i) {
-      const int t = min(max(tid + 256 * i - HALO, 0), T - 1);
+      const int t = min(max(tid + 256 * i - HALO, 0), Te - 1);
       const float2* pp = reinterpret_cast<const float2*>(S) + (size_t)(b * T + t) * NT;
 #pragma unroll
       for (int k = 0; k < 16; ++k) q[i][k] = k < NT ? pp[k] : make_float2(0.f, 0.f);
@@ -1128,7 +1142,7 @@ __global__ __launch_bounds__(256) void dwgn_small_kernel(const float* __restrict
   } else {
 #pragma unroll
     for (int i = 0; i < NSR; ++i) {
-      const int t = min(max(tid + 256 * i - HALO, 0), T - 1);
+      const int t = min(max(tid + 256 * i - HALO, 0), Te - 1);
       row_stats_from_partials(S, b * T + t, NT, tw, eps_ln, rmean[i], rrstd[i]);
     }
   }
@@ -1147,11 +1161,11 @@ __global__ __launch_bounds__(256) void dwgn_small_kernel(const float* __restrict
 #pragma unroll
   for (int i = 0; i < NSR; ++i) {
     const int r = tid + 256 * i, t = r - HALO;
-    if (r >= T + 2 * HALO) break;
+    if (r >= Te + 2 * HALO) break;
     float o[CG];
 #pragma unroll
     for (int e = 0; e < CG; ++e) o[e] = 0.f;
-    if (t >= 0 && t < T) {
+    if (t >= 0 && t < Te) {
       const float mean = rmean[i], rstd = rrstd[i];
       const float xs[CG] = {xv[i][0].x, xv[i][0].y, xv[i][0].z, xv[i][0].w, xv[i][1].x, xv[i][1].y, xv[i][1].z, xv[i][1].w};
 #pragma unroll
@@ -1170,7 +1184,7 @@ __global__ __launch_bounds__(256) void dwgn_small_kernel(const float* __restrict
 #pragma unroll
   for (int j = 0; j < WIN; ++j) win[j] = *reinterpret_cast<const dg_f2*>(hs + (rg * RPT + j) * CG + 2 * p);
   dg_f2 dv[RPT];
-  const int nv = T - rg * RPT;  // valid frames of this thread (may be <= 0); rows past T are discarded
+  const int nv = Te - rg * RPT;  // valid frames of this thread (may be <= 0); rows past Te are discarded
   dg_f2 s = {0.f, 0.f};
 #pragma unroll
   for (int q = 0; q < RPT; ++q) {
@@ -1191,7 +1205,7 @@ __global__ __launch_bounds__(256) void dwgn_small_kernel(const float* __restrict
     return dg_add1(dg_add1(dg_add1(red[slot][0][p], red[slot][1][p]), red[slot][2][p]), red[slot][3][p]);
   };
   FL_STAMP(3);
-  const float invT = 1.0f / (float)T;
+  const float invT = 1.0f / (float)Te;
   const dg_f2 mean = block_sum(s, 0) * invT;
   dg_f2 s2 = {0.f, 0.f};
 #pragma unroll
@@ -1216,14 +1230,14 @@ __global__ __launch_bounds__(256) void dwgn_small_kernel(const float* __restrict
 }
 
 constexpr int kDgSmallMaxT = 576;  // 64 row groups x RPT <= 9
-template <bool AFF>
+template <bool AFF, class End = SeqEnd<false>>
 static int launch_dwgn_small(const float* X, int H, const float* S, int NT, int tw, ModRef mod, const float* lnw, const float* lnb,
                              const float* dww, const float* dwb, const float* gnw, const float* gnb, bf16* A, int B, int T,
-                             hipStream_t st) {
+                             hipStream_t st, End end = End()) {
   FL_REQUIRE(H % 8 == 0 && T >= 1 && T <= kDgSmallMaxT && mod.div % T == 0 && NT <= 32, "dwgn_small: H=%d T=%d div=%d NT=%d", H, T,
              mod.div, NT);
   const dim3 g(H / 8, B), blk(256);
-#define FL_DWGNS(R) hipLaunchKernelGGL((dwgn_small_kernel<AFF, R>), g, blk, 0, st, X, H, S, NT, tw, 1e-6f, mod, lnw, lnb, dww, dwb, gnw, gnb, A, T)
+#define FL_DWGNS(R) hipLaunchKernelGGL((dwgn_small_kernel<AFF, R, End>), g, blk, 0, st, X, H, S, NT, tw, 1e-6f, mod, lnw, lnb, dww, dwb, gnw, gnb, A, T, end)
   if (T <= 64) FL_DWGNS(1);
   else if (T <= 192) FL_DWGNS(3);
   else if (T <= 320) FL_DWGNS(5);
@@ -1339,18 +1353,25 @@ struct LoadGN {
 // FinalLayer conv_out (k=3, pad=1) from the tap-stacked GEMM Y[m] = [W_0; W_1; W_2] x_mod[m]:
 // v[t] = b + Y0[t-1] + Y1[t] + Y2[t+1] within each utterance; then xt += dt*v (or v_out = v).
 // `src` (null: xt itself) is the state the update starts from (the fused solve's last step).
+// Exact lengths (End): the utterance's last row takes no Y2 of the row behind it, and rows from its end on are not
+// written (neither xt nor vout).
+template <class End = SeqEnd<false>>
 __global__ void conv3_combine_kernel(const float* __restrict__ Y, const float* __restrict__ bias, float* xt,
                                      float* __restrict__ vout, int M, int T, int C, float dt, int* step_ctr,
-                                     const float* src = nullptr) {
+                                     const float* src, End end) {
   size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (step_ctr && idx == 0) *step_ctr += 1;  // last kernel of the step; nothing in it reads the counter
   if (idx >= (size_t)M * C) return;
   int m = idx / C, n = idx - (size_t)m * C;
   int t = m % T;
+  const int Te = end.end(m / T, T);
+  if constexpr (End::kExact) {
+    if (t >= Te) return;
+  }
   const size_t ld = 3 * (size_t)C;
   float v = bias[n] + Y[m * ld + C + n];
   if (t > 0) v += Y[(m - 1) * ld + n];
-  if (t < T - 1) v += Y[(m + 1) * ld + 2 * C + n];
+  if (t < Te - 1) v += Y[(m + 1) * ld + 2 * C + n];
   if (vout) {
     vout[idx] = v;
   } else {
@@ -1361,11 +1382,17 @@ __global__ void conv3_combine_kernel(const float* __restrict__ Y, const float* _
 // Two-stage second-order solvers (flamed_den_solve_rk2) on the launch path: the state update behind each velocity
 // evaluation, xo = xb + c1 (y - xb) + g v.  First evaluation of a step (y null): the stage state xo = y = xb + (a dt) v;
 // second: the step itself, xo = xb in place, g = c2 dt.  Explicit roundings, so the eager and the captured solve agree
-// bitwise (no contraction into FMAs).
+// bitwise (no contraction into FMAs).  Exact lengths (End; rows of C values, T per utterance): rows from the utterance's
+// end on are neither read nor written.
+template <class End = SeqEnd<false>>
 __global__ void rk2_update_kernel(const float* xb, const float* y, const float* __restrict__ v, float* xo, size_t n, float c1,
-                                  float g) {
+                                  float g, int T, int C, End end) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= n) return;
+  if constexpr (End::kExact) {
+    const int m = (int)(idx / C);
+    if (m % T >= end.end(m / T, T)) return;
+  }
   const float b = xb[idx];
   const float base = y ? __fadd_rn(b, __fmul_rn(c1, __fsub_rn(y[idx], b))) : b;
   xo[idx] = __fadd_rn(base, __fmul_rn(g, v[idx]));
@@ -1378,7 +1405,9 @@ __global__ void rk2_update_kernel(const float* xb, const float* y, const float* 
 // column-tile-0 workgroups while every column tile reads src); the loader's prologue advances the step
 // counter (nothing in proj_in reads it).  Step 0 starts from euler_init_kernel's image: src = x_0,
 // Y1 = -b, Y0 = Y2 = 0, so v = b + (-b) = 0 exactly and x_0 passes through.
-template <typename DT>
+// Exact lengths (End): the neighbour test of the utterance's last row is t < len - 1 (a select: Y of the row behind it is
+// not read), and rows from its end on are not written to dst (they still feed proj_in rows nobody uses).
+template <typename DT, class End = SeqEnd<false>>
 struct LoadEulerIn {
   const float* __restrict__ src;
   float* dst;
@@ -1387,9 +1416,11 @@ struct LoadEulerIn {
   int* ctr;
   float dt;
   int T, C;
+  End end;
   static constexpr int EPC = DTraits<DT>::EPC;
   static constexpr int kSrcBytes = 4;
   struct Raw { float x[EPC], b[EPC], y1[EPC], y0[EPC], y2[EPC]; int t; };
+  __device__ int te(int m) const { return end.end(m / T, T); }  // (T itself in the dense form)
   static constexpr int stat_rows(int) { return 0; }
   __device__ void prologue(int, int, int, float*) const {
     if (ctr && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) *ctr += 1;
@@ -1397,12 +1428,13 @@ struct LoadEulerIn {
   __device__ Raw issue(int m, int k) const {
     Raw r;
     r.t = m % T;
+    const int Te = te(m);
     const size_t ld = 3 * (size_t)C;
 #pragma unroll
     for (int j = 0; j < EPC; j += 4) {
       float4 a = ld4(src + (size_t)m * C + k + j), b = ld4(bias + k + j), y1 = ld4(Y + (size_t)m * ld + C + k + j);
       float4 y0 = r.t > 0 ? ld4(Y + (size_t)(m - 1) * ld + k + j) : make_float4(0.f, 0.f, 0.f, 0.f);
-      float4 y2 = r.t < T - 1 ? ld4(Y + (size_t)(m + 1) * ld + 2 * C + k + j) : make_float4(0.f, 0.f, 0.f, 0.f);
+      float4 y2 = r.t < Te - 1 ? ld4(Y + (size_t)(m + 1) * ld + 2 * C + k + j) : make_float4(0.f, 0.f, 0.f, 0.f);
       r.x[j] = a.x; r.x[j + 1] = a.y; r.x[j + 2] = a.z; r.x[j + 3] = a.w;
       r.b[j] = b.x; r.b[j + 1] = b.y; r.b[j + 2] = b.z; r.b[j + 3] = b.w;
       r.y1[j] = y1.x; r.y1[j + 1] = y1.y; r.y1[j + 2] = y1.z; r.y1[j + 3] = y1.w;
@@ -1414,14 +1446,15 @@ struct LoadEulerIn {
   template <typename D>
   __device__ u32x4 finish(const Raw& r, int m, int k, const float*, int) const {
     float o[EPC];
+    const int Te = te(m);
 #pragma unroll
     for (int j = 0; j < EPC; ++j) {
       float v = r.b[j] + r.y1[j];
       if (r.t > 0) v += r.y0[j];
-      if (r.t < T - 1) v += r.y2[j];
+      if (r.t < Te - 1) v += r.y2[j];
       o[j] = __fadd_rn(r.x[j], __fmul_rn(dt, v));
     }
-    if (blockIdx.x == 0) {
+    if (blockIdx.x == 0 && (!End::kExact || r.t < Te)) {
 #pragma unroll
       for (int j = 0; j < EPC; j += 4)
         *reinterpret_cast<float4*>(dst + (size_t)m * C + k + j) = make_float4(o[j], o[j + 1], o[j + 2], o[j + 3]);
@@ -1512,13 +1545,16 @@ thread_local bf16* g_a16 = nullptr;  // the calling thread's step workspace (set
 // reads (A16) -- conv3_combine_kernel's arithmetic in its order, then cast_bf16x8_kernel's, so the solve is
 // bitwise the unfused one -- in ONE streaming pass instead of a combine launch at the end of the step and a
 // cast launch at its start.  Thread 0 advances the step counter (nothing here or in proj_in reads it).
+// Exact lengths (End): neighbour test at the utterance's own end; rows behind it keep their xt (a16 still gets a row).
+template <class End = SeqEnd<false>>
 __global__ void euler_cast_kernel(float* xt, const float* __restrict__ Y, const float* __restrict__ bias,
-                                  bf16* __restrict__ a16, int M, int T, int C, float dt, int* step_ctr) {
+                                  bf16* __restrict__ a16, int M, int T, int C, float dt, int* step_ctr, End end) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (step_ctr && i == 0) *step_ctr += 1;
   const int C8 = C / 8;
   if (i >= (size_t)M * C8) return;
   const int m = i / C8, k = (int)(i - (size_t)m * C8) * 8, t = m % T;
+  const int Te = end.end(m / T, T);
   const size_t ld = 3 * (size_t)C;
   float x[8], o[8];
   {
@@ -1529,19 +1565,21 @@ __global__ void euler_cast_kernel(float* xt, const float* __restrict__ Y, const 
   for (int h = 0; h < 8; h += 4) {
     const float4 bb = ld4(bias + k + h), y1 = ld4(Y + (size_t)m * ld + C + k + h);
     const float4 y0 = t > 0 ? ld4(Y + (size_t)(m - 1) * ld + k + h) : make_float4(0.f, 0.f, 0.f, 0.f);
-    const float4 y2 = t < T - 1 ? ld4(Y + (size_t)(m + 1) * ld + 2 * C + k + h) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 y2 = t < Te - 1 ? ld4(Y + (size_t)(m + 1) * ld + 2 * C + k + h) : make_float4(0.f, 0.f, 0.f, 0.f);
     const float bv[4] = {bb.x, bb.y, bb.z, bb.w}, v1[4] = {y1.x, y1.y, y1.z, y1.w};
     const float v0[4] = {y0.x, y0.y, y0.z, y0.w}, v2[4] = {y2.x, y2.y, y2.z, y2.w};
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float v = bv[e] + v1[e];
       if (t > 0) v += v0[e];
-      if (t < T - 1) v += v2[e];
+      if (t < Te - 1) v += v2[e];
       o[h + e] = __fadd_rn(x[h + e], __fmul_rn(dt, v));
     }
   }
-  *reinterpret_cast<float4*>(xt + (size_t)m * C + k) = make_float4(o[0], o[1], o[2], o[3]);
-  *reinterpret_cast<float4*>(xt + (size_t)m * C + k + 4) = make_float4(o[4], o[5], o[6], o[7]);
+  if (!End::kExact || t < Te) {
+    *reinterpret_cast<float4*>(xt + (size_t)m * C + k) = make_float4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<float4*>(xt + (size_t)m * C + k + 4) = make_float4(o[4], o[5], o[6], o[7]);
+  }
   *reinterpret_cast<u32x4*>(a16 + (size_t)m * C + k) = pack_chunk<bf16>(o);
 }
 
@@ -1807,6 +1845,9 @@ struct Den {
   int g_B = -1, g_T = -1, g_nfe = -1, g_epoch = -1;
   double g_a = 0.0;  // stage parameter of the cached graph's solver (0: Euler)
   const void *g_xt = nullptr, *g_mods = nullptr, *g_ws = nullptr;
+  const int* g_lens = nullptr;  // ... and its lengths array (exact lengths; null: a dense solve's graph)
+  DevLens dlens;               // device copy of an exact-lengths call's lengths (launch path), filled in stream order per call
+  int lens_path = -1;          // how the last _lens solve ran (flamed_den_lens_path)
   int* ctr = nullptr;  // device Euler step counter for graph replay
   int* scnt = nullptr;  // split-K tile counters (zeroed at load; every launch leaves them zero)
   static constexpr int kSplitCounters = 16384;
@@ -2025,6 +2066,7 @@ FLAMED_API int flamed_den_destroy(flamed_den_t h) {
     if (d->ctr) (void)hipFree(d->ctr);
     if (d->scnt) (void)hipFree(d->scnt);
     if (d->gcnt) (void)hipFree(d->gcnt);
+    d->dlens.release();
     persist_release(d);
     if (d->dev) (void)hipFree(d->dev);
   }
@@ -2083,6 +2125,8 @@ FLAMED_API int flamed_den_load(flamed_den_t h, const float* const* w, int n, hip
     if (d->ctr) { (void)hipFree(d->ctr); d->ctr = nullptr; }
     if (d->scnt) { (void)hipFree(d->scnt); d->scnt = nullptr; }
     if (d->gcnt) { (void)hipFree(d->gcnt); d->gcnt = nullptr; }
+    d->dlens.release();
+    d->g_lens = nullptr;
     persist_release(d);
     if (d->dev) { (void)hipFree(d->dev); d->dev = nullptr; }
     d->pdev_ok = -1;
@@ -2354,12 +2398,12 @@ FLAMED_API int flamed_den_chain_info(flamed_den_t h, int* parked, int* retries) 
 namespace fl {
 
 // Large-M fused Euler step: euler_cast_kernel (x_{s-1} -> x_s in place, bf16 x_s into A16) + proj_in on A16.
-template <typename XT>
-static int big_euler_proj_in(Den* d, float* xt, const DenWs& w, XT* X, int* ctr, float dt, int M, int T, hipStream_t st) {
+template <typename XT, class End>
+static int big_euler_proj_in(Den* d, float* xt, const DenWs& w, XT* X, int* ctr, float dt, int M, int T, hipStream_t st, End end) {
   const int H = d->H, C = d->C;
   FL_REQUIRE(w.A16 && C % 8 == 0, "den_step: large-M fused Euler step needs the A16 buffer");
   const size_t n = (size_t)M * (C / 8);
-  hipLaunchKernelGGL(euler_cast_kernel, dim3((n + 255) / 256), dim3(256), 0, st, xt, w.Y, d->bout, w.A16, M, T, C, dt, ctr);
+  hipLaunchKernelGGL(euler_cast_kernel<End>, dim3((n + 255) / 256), dim3(256), 0, st, xt, w.Y, d->bout, w.A16, M, T, C, dt, ctr, end);
   FL_LAUNCH_CHECK();
   const GemmCfg cfg = kCfgLarge;
   const int NT = H / 128;
@@ -2370,9 +2414,12 @@ static int big_euler_proj_in(Den* d, float* xt, const DenWs& w, XT* X, int* ctr,
 // One velocity evaluation (+ Euler update when vout == nullptr).
 // `ctr` (optional): device step counter; when set the modulation rows are read at
 // mods + (*ctr) * B * MS and the last kernel increments it (graph replay of captured steps).
-template <typename DT, typename XT>
+// End = SeqEnd<true> (exact lengths, den_solve_lens): the same launches on the same (B, T) layout; the kernels that look
+// across rows -- the depthwise conv + GroupNorm sub-block, the conv_out tap combine and the state update -- end every
+// utterance at its own length, everything else is row-local and computes the padding rows for nobody.
+template <typename DT, typename XT, class End>
 static int den_step_impl(Den* d, float* xt, const float* mods, int mod_div, int B, int T, float dt, float* vout,
-                         const DenWs& w, int* ctr, hipStream_t st, const float* xsrc, int Bs, int chain, int nchains) {
+                         const DenWs& w, int* ctr, hipStream_t st, const float* xsrc, int Bs, int chain, int nchains, End end) {
   const int M = B * T, H = d->H, C = d->C, MS = d->MS;
   const Tune& tu = tn();
   // a step's modulation rows are Bs apart (Bs = B, or the whole batch when this is one of its sub-batches)
@@ -2435,9 +2482,9 @@ static int den_step_impl(Den* d, float* xt, const float* mods, int mod_div, int 
   FL_REQUIRE(!xsrc || !vout, "den_step: a fused Euler step has no velocity output");
   FL_REQUIRE(!xsrc || !big || xsrc == xt, "den_step: the large-M fused Euler step updates the state in place");
   if (xsrc && big) {  // large M: the previous step's combine + Euler update and proj_in's bf16 cast in one pass
-    if constexpr (std::is_same<DT, bf16>::value) K_(0, big_euler_proj_in<XT>(d, xt, w, X, ctr, dt, M, T, st));
+    if constexpr (std::is_same<DT, bf16>::value) K_(0, big_euler_proj_in<XT>(d, xt, w, X, ctr, dt, M, T, st, end));
   } else if (xsrc) {
-    const LoadEulerIn<DT> le{xsrc, xt, w.Y, d->bout, ctr, dt, T, C};
+    const LoadEulerIn<DT, End> le{xsrc, xt, w.Y, d->bout, ctr, dt, T, C, end};
     const EpiBiasStatsT<false, XT> ep{d->bin, X, H, w.S0, NT};
     if (cfg == kCfgTiny) K_(0, (launch_gemm_cfg<32, 32, 3, DT>(le, (const DT*)d->win, C, ep, M, H, C, st)));
     else K_(0, (launch_gemm_auto<DT>(cfg, le, (const DT*)d->win, C, ep, M, H, C, st)));
@@ -2450,8 +2497,8 @@ static int den_step_impl(Den* d, float* xt, const float* mods, int mod_div, int 
     ModRef mc{md, md + H, MS, mod_div, so};
     ModRef mm{md + 3 * H, md + 4 * H, MS, mod_div, so};
     if (f8) {
-      K_(1, (launch_dwconv_stats<true, XT>(X, H, w.S0, NT, BN, mc, Bw.lnw, Bw.lnb, Bw.dww, Bw.dwb, Dx, w.GP, w.GNS, B, T, st, 1, gcnt)));
-      K_(2, (launch_dwconv_stats<true, XT>(X, H, w.S0, NT, BN, mc, Bw.lnw, Bw.lnb, Bw.dww, Bw.dwb, Dx, w.GP, w.GNS, B, T, st, 2, gcnt)));
+      K_(1, (launch_dwconv_stats<true, XT, End>(X, H, w.S0, NT, BN, mc, Bw.lnw, Bw.lnb, Bw.dww, Bw.dwb, Dx, w.GP, w.GNS, B, T, st, 1, gcnt, end)));
+      K_(2, (launch_dwconv_stats<true, XT, End>(X, H, w.S0, NT, BN, mc, Bw.lnw, Bw.lnb, Bw.dww, Bw.dwb, Dx, w.GP, w.GNS, B, T, st, 2, gcnt, end)));
       K_(3, f8_prep(LoadGN<bf16>{w.D, H, w.GNS, Bw.gnw, Bw.gnb, T, D16p}, M, A8, A8s, st));
       K_(3, launch_gemm8p_f8(A8, A8s, H, Bw.q[0], Bw.qs[0], H, EpiBiasActF8<1>{Bw.b2, U8, U8s, H}, M, H, H, st));
       K_(4, launch_gemm8p_f8(U8, U8s, H, Bw.q[1], Bw.qs[1], H,
@@ -2464,14 +2511,14 @@ static int den_step_impl(Den* d, float* xt, const float* mods, int mod_div, int 
       continue;
     }
     if (dwgn) {  // large M: conv + GroupNorm in one kernel, conv_2 on the normalised bf16 rows
-      K_(1, (launch_dwgn<true, XT>(X, H, w.S0, NT, BN, mc, Bw.lnw, Bw.lnb, Bw.dww, Bw.dwb, Bw.gnw, Bw.gnb, w.A16, B, T, st)));
+      K_(1, (launch_dwgn<true, XT, End>(X, H, w.S0, NT, BN, mc, Bw.lnw, Bw.lnb, Bw.dww, Bw.dwb, Bw.gnw, Bw.gnb, w.A16, B, T, st, end)));
       K_(3, (den_gemm<DT>(cfg, false, LoadPlain<DT>{(const DT*)w.A16, H}, (const DT*)Bw.w2, H, EpiBiasAct<DT, 1>{Bw.b2, U, H}, M, H, H, st)));
     } else if (dwgn_s) {
-      K_(1, (launch_dwgn_small<true>((const float*)w.X, H, w.S0, NT, BN, mc, Bw.lnw, Bw.lnb, Bw.dww, Bw.dwb, Bw.gnw, Bw.gnb, As, B, T, st)));
+      K_(1, (launch_dwgn_small<true, End>((const float*)w.X, H, w.S0, NT, BN, mc, Bw.lnw, Bw.lnb, Bw.dww, Bw.dwb, Bw.gnw, Bw.gnb, As, B, T, st, end)));
       K_(3, (den_gemm<DT>(cfg, false, LoadPlain<DT>{(const DT*)As, H}, (const DT*)Bw.w2, H, EpiBiasAct<DT, 1>{Bw.b2, U, H}, M, H, H, st)));
     } else {
-      K_(1, (launch_dwconv_stats<true, XT>(X, H, w.S0, NT, BN, mc, Bw.lnw, Bw.lnb, Bw.dww, Bw.dwb, Dx, w.GP, w.GNS, B, T, st, 1, gcnt)));
-      K_(2, (launch_dwconv_stats<true, XT>(X, H, w.S0, NT, BN, mc, Bw.lnw, Bw.lnb, Bw.dww, Bw.dwb, Dx, w.GP, w.GNS, B, T, st, 2, gcnt)));
+      K_(1, (launch_dwconv_stats<true, XT, End>(X, H, w.S0, NT, BN, mc, Bw.lnw, Bw.lnb, Bw.dww, Bw.dwb, Dx, w.GP, w.GNS, B, T, st, 1, gcnt, end)));
+      K_(2, (launch_dwconv_stats<true, XT, End>(X, H, w.S0, NT, BN, mc, Bw.lnw, Bw.lnb, Bw.dww, Bw.dwb, Dx, w.GP, w.GNS, B, T, st, 2, gcnt, end)));
       K_(3, (den_gemm<DT>(cfg, true, LoadGN<DT>{w.D, H, w.GNS, Bw.gnw, Bw.gnb, T, D16p}, (const DT*)Bw.w2, H,
                                           EpiBiasAct<DT, 1>{Bw.b2, U, H}, M, H, H, st)));
     }
@@ -2498,19 +2545,19 @@ static int den_step_impl(Den* d, float* xt, const float* mods, int mod_div, int 
   ModRef mo{mf + 3 * H, mf + 4 * H, MS, mod_div, so};
   const DenBlockW& F = d->fin;
   if (f8) {
-    K_(1, (launch_dwconv_stats<false, XT>(X, H, w.S0, NT, BN, mc, nullptr, nullptr, F.dww, F.dwb, Dx, w.GP, w.GNS, B, T, st, 1, gcnt)));
-    K_(2, (launch_dwconv_stats<false, XT>(X, H, w.S0, NT, BN, mc, nullptr, nullptr, F.dww, F.dwb, Dx, w.GP, w.GNS, B, T, st, 2, gcnt)));
+    K_(1, (launch_dwconv_stats<false, XT, End>(X, H, w.S0, NT, BN, mc, nullptr, nullptr, F.dww, F.dwb, Dx, w.GP, w.GNS, B, T, st, 1, gcnt, end)));
+    K_(2, (launch_dwconv_stats<false, XT, End>(X, H, w.S0, NT, BN, mc, nullptr, nullptr, F.dww, F.dwb, Dx, w.GP, w.GNS, B, T, st, 2, gcnt, end)));
     K_(3, f8_prep(LoadGN<bf16>{w.D, H, w.GNS, F.gnw, F.gnb, T, D16p}, M, A8, A8s, st));
     K_(3, launch_gemm8p_f8(A8, A8s, H, F.q[0], F.qs[0], H, EpiBiasActF8<1>{F.b2, U8, U8s, H}, M, H, H, st));
   } else if (dwgn) {
-    K_(1, (launch_dwgn<false, XT>(X, H, w.S0, NT, BN, mc, nullptr, nullptr, F.dww, F.dwb, F.gnw, F.gnb, w.A16, B, T, st)));
+    K_(1, (launch_dwgn<false, XT, End>(X, H, w.S0, NT, BN, mc, nullptr, nullptr, F.dww, F.dwb, F.gnw, F.gnb, w.A16, B, T, st, end)));
     K_(3, (den_gemm<DT>(cfg, false, LoadPlain<DT>{(const DT*)w.A16, H}, (const DT*)F.w2, H, EpiBiasAct<DT, 1>{F.b2, U, H}, M, H, H, st)));
   } else if (dwgn_s) {
-    K_(1, (launch_dwgn_small<false>((const float*)w.X, H, w.S0, NT, BN, mc, nullptr, nullptr, F.dww, F.dwb, F.gnw, F.gnb, As, B, T, st)));
+    K_(1, (launch_dwgn_small<false, End>((const float*)w.X, H, w.S0, NT, BN, mc, nullptr, nullptr, F.dww, F.dwb, F.gnw, F.gnb, As, B, T, st, end)));
     K_(3, (den_gemm<DT>(cfg, false, LoadPlain<DT>{(const DT*)As, H}, (const DT*)F.w2, H, EpiBiasAct<DT, 1>{F.b2, U, H}, M, H, H, st)));
   } else {
-    K_(1, (launch_dwconv_stats<false, XT>(X, H, w.S0, NT, BN, mc, nullptr, nullptr, F.dww, F.dwb, Dx, w.GP, w.GNS, B, T, st, 1, gcnt)));
-    K_(2, (launch_dwconv_stats<false, XT>(X, H, w.S0, NT, BN, mc, nullptr, nullptr, F.dww, F.dwb, Dx, w.GP, w.GNS, B, T, st, 2, gcnt)));
+    K_(1, (launch_dwconv_stats<false, XT, End>(X, H, w.S0, NT, BN, mc, nullptr, nullptr, F.dww, F.dwb, Dx, w.GP, w.GNS, B, T, st, 1, gcnt, end)));
+    K_(2, (launch_dwconv_stats<false, XT, End>(X, H, w.S0, NT, BN, mc, nullptr, nullptr, F.dww, F.dwb, Dx, w.GP, w.GNS, B, T, st, 2, gcnt, end)));
     K_(3, (den_gemm<DT>(cfg, true, LoadGN<DT>{w.D, H, w.GNS, F.gnw, F.gnb, T, D16p}, (const DT*)F.w2, H, EpiBiasAct<DT, 1>{F.b2, U, H}, M, H, H, st)));
   }
   if (f8) {
@@ -2536,10 +2583,12 @@ static int den_step_impl(Den* d, float* xt, const float* mods, int mod_div, int 
   }
   if (!xsrc) {
     size_t n = (size_t)M * C;
-    hipLaunchKernelGGL(conv3_combine_kernel, dim3((n + 255) / 256), dim3(256), 0, st, w.Y, d->bout, xt, vout, M, T, C, dt, ctr, nullptr);
+    hipLaunchKernelGGL(conv3_combine_kernel<End>, dim3((n + 255) / 256), dim3(256), 0, st, w.Y, d->bout, xt, vout, M, T, C, dt, ctr,
+                       (const float*)nullptr, end);
     FL_LAUNCH_CHECK();
     if (tu.dup_class == 8) {  // duplicate without a second counter increment
-      hipLaunchKernelGGL(conv3_combine_kernel, dim3((n + 255) / 256), dim3(256), 0, st, w.Y, d->bout, xt, vout, M, T, C, dt, nullptr, nullptr);
+      hipLaunchKernelGGL(conv3_combine_kernel<End>, dim3((n + 255) / 256), dim3(256), 0, st, w.Y, d->bout, xt, vout, M, T, C, dt,
+                         (int*)nullptr, (const float*)nullptr, end);
       FL_LAUNCH_CHECK();
     }
   }
@@ -2548,17 +2597,26 @@ static int den_step_impl(Den* d, float* xt, const float* mods, int mod_div, int 
   return kOk;
 }
 
-static int den_step(Den* d, float* xt, const float* mods, int mod_div, int B, int T, float dt, float* vout, void* ws,
-                    hipStream_t st, int* ctr = nullptr, const float* xsrc = nullptr, int Bs = 0, int chain = 0,
-                    int nchains = 1) {
+template <class End>
+static int den_step_end(Den* d, float* xt, const float* mods, int mod_div, int B, int T, float dt, float* vout, void* ws,
+                        hipStream_t st, int* ctr, const float* xsrc, int Bs, int chain, int nchains, End end) {
   if (Bs <= 0) Bs = B;
   DenWs w;
   den_ws_layout(d, B, T, ws, &w);
   if (d->dt == FLAMED_BF16) {
-    if (den_x16(d, B, T)) return den_step_impl<bf16, bf16>(d, xt, mods, mod_div, B, T, dt, vout, w, ctr, st, xsrc, Bs, chain, nchains);
-    return den_step_impl<bf16, float>(d, xt, mods, mod_div, B, T, dt, vout, w, ctr, st, xsrc, Bs, chain, nchains);
+    if (den_x16(d, B, T))
+      return den_step_impl<bf16, bf16>(d, xt, mods, mod_div, B, T, dt, vout, w, ctr, st, xsrc, Bs, chain, nchains, end);
+    return den_step_impl<bf16, float>(d, xt, mods, mod_div, B, T, dt, vout, w, ctr, st, xsrc, Bs, chain, nchains, end);
   }
-  return den_step_impl<float, float>(d, xt, mods, mod_div, B, T, dt, vout, w, ctr, st, xsrc, Bs, chain, nchains);
+  return den_step_impl<float, float>(d, xt, mods, mod_div, B, T, dt, vout, w, ctr, st, xsrc, Bs, chain, nchains, end);
+}
+// lens (B device ints, or null = dense): the utterances' own lengths of an exact-lengths solve
+static int den_step(Den* d, float* xt, const float* mods, int mod_div, int B, int T, float dt, float* vout, void* ws,
+                    hipStream_t st, int* ctr = nullptr, const float* xsrc = nullptr, int Bs = 0, int chain = 0,
+                    int nchains = 1, const int* lens = nullptr) {
+  if (lens)
+    return den_step_end(d, xt, mods, mod_div, B, T, dt, vout, ws, st, ctr, xsrc, Bs, chain, nchains, SeqEnd<true>::make(lens, 1));
+  return den_step_end(d, xt, mods, mod_div, B, T, dt, vout, ws, st, ctr, xsrc, Bs, chain, nchains, SeqEnd<false>());
 }
 
 // The fused Euler step (LoadEulerIn) runs where proj_in takes the small-M register loop with one
@@ -2781,6 +2839,32 @@ static int persist_solve(Den* d, float* xt, const float* mods, int nfe, int B, i
     ++d->pring_n;
   }
   ++d->pruns;
+  return kOk;
+}
+
+// The solve's own launches of the state-update kernels: dense, or (lens: B device ints) ending every utterance at its length.
+static int launch_combine(const float* Y, const float* bias, float* xt, int M, int T, int C, float dt, const float* src,
+                          const int* lens, hipStream_t st) {
+  const size_t n = (size_t)M * C;
+  if (lens)
+    hipLaunchKernelGGL(conv3_combine_kernel<SeqEnd<true>>, dim3((n + 255) / 256), dim3(256), 0, st, Y, bias, xt, (float*)nullptr, M, T,
+                       C, dt, (int*)nullptr, src, SeqEnd<true>::make(lens, 1));
+  else
+    hipLaunchKernelGGL(conv3_combine_kernel<SeqEnd<false>>, dim3((n + 255) / 256), dim3(256), 0, st, Y, bias, xt, (float*)nullptr, M, T,
+                       C, dt, (int*)nullptr, src, SeqEnd<false>());
+  FL_LAUNCH_CHECK();
+  return kOk;
+}
+static int launch_rk2_update(const float* xb, const float* y, const float* v, float* xo, int M, int T, int C, float c1, float g,
+                             const int* lens, hipStream_t st) {
+  const size_t n = (size_t)M * C;
+  if (lens)
+    hipLaunchKernelGGL(rk2_update_kernel<SeqEnd<true>>, dim3((n + 255) / 256), dim3(256), 0, st, xb, y, v, xo, n, c1, g, T, C,
+                       SeqEnd<true>::make(lens, 1));
+  else
+    hipLaunchKernelGGL(rk2_update_kernel<SeqEnd<false>>, dim3((n + 255) / 256), dim3(256), 0, st, xb, y, v, xo, n, c1, g, T, C,
+                       SeqEnd<false>());
+  FL_LAUNCH_CHECK();
   return kOk;
 }
 
@@ -3021,8 +3105,12 @@ static int den_chain_streams(Den* d, int S, hipStream_t st) {
 // rk2_update_kernel; modulation row block k belongs to evaluation k on every path.
 // mod_B > 0 (the exact-lengths fallback, plain launches only): xt is a sub-batch of B utterances whose modulation rows
 // lie in the table of a batch of mod_B, so row block k starts k * mod_B rows in.
+// dlens (B device ints, the handle's DevLens, written in stream order ahead of this call; null = dense): the ragged batch
+// of an exact-lengths solve -- every step variant below on the same (B, T) layout with every utterance ended at its own
+// length (den_step_impl).  The captured graphs hold the array's address, never a length.
 static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe, int B, int T, void* ws, size_t ws_bytes,
-                           int use_graph, int s0, int s1, const Rk2* rk, hipStream_t st, int mod_B = 0) {
+                           int use_graph, int s0, int s1, const Rk2* rk, hipStream_t st, int mod_B = 0,
+                           const int* dlens = nullptr) {
   Den* d = reinterpret_cast<Den*>(h);
   FL_REQUIRE(d && d->dev, "flamed_den_solve: handle not loaded");
   FL_REQUIRE(xt && mods && ws && B > 0 && T > 0 && nfe > 0, "flamed_den_solve: bad args");
@@ -3045,6 +3133,7 @@ static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe
     mk = mods + (size_t)k * Bk * d->MS;
     wk = static_cast<char*>(ws) + k * wsk;
   };
+  auto lens_of = [&](int k) -> const int* { return dlens ? dlens + (size_t)k * Bk : nullptr; };  // chain k's lengths
   // evaluation e of a two-stage solve on chain k: v(x) into XV, then y = x + (a dt) v into XP (e even), or v(y)
   // and the step x += c1 (y - x) + (c2 dt) v in place (e odd)
   auto rk_eval = [&](int e, int k, const float* mrow, hipStream_t cs, int* ctr) -> int {
@@ -3053,13 +3142,10 @@ static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe
     DenWs wc;
     den_ws_layout(d, Bk, T, wk, &wc);
     const bool first = !(e & 1);
-    const int rc = den_step(d, first ? xk : wc.XP, mrow ? mrow : mk, T, Bk, T, 0.f, wc.XV, wk, cs, ctr, nullptr, B, k, S);
+    const int rc = den_step(d, first ? xk : wc.XP, mrow ? mrow : mk, T, Bk, T, 0.f, wc.XV, wk, cs, ctr, nullptr, B, k, S, lens_of(k));
     if (rc) return rc;
-    const size_t nk = (size_t)Bk * T * d->C;
-    hipLaunchKernelGGL(rk2_update_kernel, dim3((nk + 255) / 256), dim3(256), 0, cs, xk, first ? (const float*)nullptr : wc.XP,
-                       wc.XV, first ? wc.XP : xk, nk, first ? 0.f : rk->c1, first ? rk->adt : rk->c2dt);
-    FL_LAUNCH_CHECK();
-    return kOk;
+    return launch_rk2_update(xk, first ? (const float*)nullptr : wc.XP, wc.XV, first ? wc.XP : xk, Bk * T, T, d->C,
+                             first ? 0.f : rk->c1, first ? rk->adt : rk->c2dt, lens_of(k), cs);
   };
   if (!(use_graph & 1)) {
     for (int s = s0; s < s1; ++s)
@@ -3067,7 +3153,7 @@ static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe
         float* xk; const float* mk; void* wk;
         sub(k, xk, mk, wk);
         int rc = rk ? rk_eval(s, k, mk + s * step_stride, st, nullptr)
-                    : den_step(d, xk, mk + s * step_stride, T, Bk, T, dt, nullptr, wk, st, nullptr, nullptr, B, k, S);
+                    : den_step(d, xk, mk + s * step_stride, T, Bk, T, dt, nullptr, wk, st, nullptr, nullptr, B, k, S, lens_of(k));
         if (rc) return rc;
       }
     return kOk;
@@ -3106,7 +3192,7 @@ static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe
   den_ws_layout(d, B, T, ws, &w);
   // the graph bakes in dt = 1/nfe (and a two-stage solver's coefficients), so nfe and the solver are part of the key
   const bool hit = d->gexec && d->g_B == B && d->g_T == T && d->g_nfe == nfe && d->g_xt == xt && d->g_mods == mods && d->g_ws == ws &&
-                   d->g_epoch == d->tune_ver && d->g_a == (rk ? rk->a : 0.0);
+                   d->g_epoch == d->tune_ver && d->g_a == (rk ? rk->a : 0.0) && d->g_lens == dlens;
   if (!hit) {
     retire_graph(d->gexec);
     for (auto& g : d->gexec_c) retire_graph(g);
@@ -3130,7 +3216,7 @@ static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe
           hipStream_t cs = k == 0 ? cap : d->cap_aux[k];
           for (int s = 0; s < G && rc == kOk; ++s)
             rc = rk ? rk_eval(s, k, nullptr, cs, d->ctr + 16 * k)
-                    : den_step(d, xk, mk, T, Bk, T, dt, nullptr, wk, cs, d->ctr + 16 * k, fbig ? xk : nullptr, B, k, S);
+                    : den_step(d, xk, mk, T, Bk, T, dt, nullptr, wk, cs, d->ctr + 16 * k, fbig ? xk : nullptr, B, k, S, lens_of(k));
         }
         for (int k = 1; k < S && rc == kOk; ++k) {
           FL_HIP(hipEventRecord(d->cap_ev[k], d->cap_aux[k]));
@@ -3148,8 +3234,8 @@ static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe
         sub(k, xk, mk, wk);
         for (int s = 0; s < G && rc == kOk; ++s) {
           if (rk) rc = rk_eval(s, k, nullptr, cap, d->ctr + 16 * k);
-          else if (fused) rc = den_step(d, s % 2 ? w.XP : xt, mods, T, B, T, dt, nullptr, ws, cap, d->ctr, s % 2 ? xt : w.XP);
-          else rc = den_step(d, xk, mk, T, Bk, T, dt, nullptr, wk, cap, d->ctr + 16 * k, fbig ? xk : nullptr, B, k, S);
+          else if (fused) rc = den_step(d, s % 2 ? w.XP : xt, mods, T, B, T, dt, nullptr, ws, cap, d->ctr, s % 2 ? xt : w.XP, 0, 0, 1, dlens);
+          else rc = den_step(d, xk, mk, T, Bk, T, dt, nullptr, wk, cap, d->ctr + 16 * k, fbig ? xk : nullptr, B, k, S, lens_of(k));
         }
         return rc;
       });
@@ -3157,6 +3243,7 @@ static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe
     }
     d->g_B = B; d->g_T = T; d->g_nfe = nfe; d->g_epoch = d->tune_ver; d->g_xt = xt; d->g_mods = mods; d->g_ws = ws;
     d->g_a = rk ? rk->a : 0.0;
+    d->g_lens = dlens;
   }
   const size_t n = (size_t)B * T * d->C;
   if (s0 == 0) {
@@ -3205,9 +3292,8 @@ static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe
   note_graph_use(d->gexec, st);
   for (int k = 1; k < (br ? 1 : S); ++k) note_graph_use(d->gexec_c[k], st);  // st has joined chain k's replays
   if (fused && s1 == nfe) {  // the last step's combine + Euler update: x_nfe = XP + dt * v (nfe even: XP holds x_{nfe-1})
-    hipLaunchKernelGGL(conv3_combine_kernel, dim3((n + 255) / 256), dim3(256), 0, st, w.Y, d->bout, xt, nullptr, B * T, T,
-                       d->C, dt, nullptr, w.XP);
-    FL_LAUNCH_CHECK();
+    const int rc = launch_combine(w.Y, d->bout, xt, B * T, T, d->C, dt, w.XP, dlens, st);
+    if (rc) return rc;
   }
   if (fbig && s1 == nfe) {  // every chain's last combine + Euler update, in place
     for (int k = 0; k < S; ++k) {
@@ -3215,10 +3301,8 @@ static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe
       sub(k, xk, mk, wk);
       DenWs wc;
       den_ws_layout(d, Bk, T, wk, &wc);
-      const size_t nk = (size_t)Bk * T * d->C;
-      hipLaunchKernelGGL(conv3_combine_kernel, dim3((nk + 255) / 256), dim3(256), 0, st, wc.Y, d->bout, xk, nullptr, Bk * T, T,
-                         d->C, dt, nullptr, nullptr);
-      FL_LAUNCH_CHECK();
+      const int rc = launch_combine(wc.Y, d->bout, xk, Bk * T, T, d->C, dt, nullptr, lens_of(k), st);
+      if (rc) return rc;
     }
   }
   return kOk;
@@ -3240,12 +3324,16 @@ FLAMED_API int flamed_den_solve_rk2(flamed_den_t h, float* xt, const float* mods
 }
 
 // Exact lengths: utterance u of the padded batch (rows u T .. u T + lens[u] - 1 of xt, modulation row u of every block)
-// solved over its own lens[u] frames, as if alone at T = lens[u]; the rows behind it are neither read nor written.
-//   * every length T: the dense solve itself (bitwise);
-//   * 2..8 utterances eligible for the persistent launch: its ragged variants, one launch;
-//   * anything else (fp32 / fp8 handles, B > 8, the chunk limits, knob persist 0, use_graph bit 2, a device that
-//     refuses the cooperative grid): one utterance after another through the range solver, plain launches against
-//     the whole batch's modulation table.  (Per-utterance lengths inside the launch-path kernels are not built.)
+// solved over its own lens[u] frames, as if alone at T = lens[u]; the rows behind it never influence a valid row and
+// are never written (the launch path's row-local kernels may read them).  In order of preference (Den::lens_path):
+//   0 every length T: the dense solve itself (bitwise); (one utterance: the dense solve of its lens[0] rows)
+//   1 2..8 utterances eligible for the persistent launch: its ragged variants, one launch;
+//   2 anything else (fp32 handles, B > 8, the chunk limits, knob persist 0, use_graph bit 2, a device that refuses the
+//     cooperative grid): the ragged batch on the launch path -- the lengths go to the handle's device array in stream
+//     order, and the range solver runs the (B, T) solve it would run dense (graph of launches, fused steps, sub-batch
+//     chains, RK2) with every utterance ended at its own length;
+//   3 fp8 handles (their MX-fp8 operand passes are not part of the ragged path) and knob ragged_launch 0: one utterance
+//     after another through the range solver, plain launches against the whole batch's modulation table.
 static int den_solve_lens(flamed_den_t h, float* xt, const float* mods, const int* lens, int nfe, int B, int T, void* ws,
                           size_t ws_bytes, int use_graph, const Rk2* rk, hipStream_t st, const char* what) {
   // host-side argument checks, before anything touches the handle or a device
@@ -3257,22 +3345,40 @@ static int den_solve_lens(flamed_den_t h, float* xt, const float* mods, const in
     FL_REQUIRE(lens[u] >= 2 && lens[u] <= T, "%s: utterance %d has length %d (2..T = %d)", what, u, lens[u], T);
     dense = dense && lens[u] == T;
   }
-  if (dense) return den_solve_range(h, xt, mods, nfe, B, T, ws, ws_bytes, use_graph, 0, nfe, rk, st);
-  // one utterance: the ordinary solve of its first lens[0] rows (the table holds one row per block either way)
-  if (B == 1) return den_solve_range(h, xt, mods, nfe, 1, lens[0], ws, ws_bytes, use_graph, 0, nfe, rk, st);
   Den* d = reinterpret_cast<Den*>(h);
   FL_REQUIRE(d->dev, "%s: handle not loaded", what);
   FL_DEN_CALL(d);
+  d->lens_path = 0;
+  if (dense) return den_solve_range(h, xt, mods, nfe, B, T, ws, ws_bytes, use_graph, 0, nfe, rk, st);
+  // one utterance: the ordinary solve of its first lens[0] rows (the table holds one row per block either way)
+  if (B == 1) return den_solve_range(h, xt, mods, nfe, 1, lens[0], ws, ws_bytes, use_graph, 0, nfe, rk, st);
   FL_REQUIRE_ON(xt, d->device, what);
   if (ws_bytes < den_solve_ws(d, B, T)) {
     set_error("%s: workspace too small", what);
     return kNoWorkspace;
   }
   if (B >= 2 && B <= pk::kGroups && !(use_graph & 2) && persist_eligible(d, B, T)) {
+    d->lens_path = 1;
     const int prc = persist_solve(d, xt, mods, nfe, B, T, 0, nfe, st, rk, lens);
     if (prc != kBadArg) return prc;
     d->pdev_ok = 0;  // the runtime refused the cooperative grid: this device never runs the persistent solve
   }
+  if (tn().ragged_launch && !d->f8) {
+    // the upload precedes the range solver's fork event, so the sub-batch chains' streams see it; a reallocated array
+    // retires the graphs that hold the old address
+    bool moved = false;
+    const int lrc = d->dlens.put(lens, B, st, &moved);
+    if (lrc) return lrc;
+    if (moved) {
+      retire_graph(d->gexec);
+      for (auto& g : d->gexec_c) retire_graph(g);
+      d->g_lens = nullptr;
+    }
+    d->lens_path = 2;
+    // (bit 2: the range solver's own persistent launch is for dense batches)
+    return den_solve_range(h, xt, mods, nfe, B, T, ws, ws_bytes, (use_graph & 1) | 2, 0, nfe, rk, st, 0, d->dlens.d);
+  }
+  d->lens_path = 3;
   for (int u = 0; u < B; ++u) {
     const int rc = den_solve_range(h, xt + (size_t)u * T * d->C, mods + (size_t)u * d->MS, nfe, 1, lens[u], ws, ws_bytes,
                                    use_graph & 2, 0, nfe, rk, st, B);
@@ -3284,6 +3390,14 @@ static int den_solve_lens(flamed_den_t h, float* xt, const float* mods, const in
 FLAMED_API int flamed_den_solve_lens(flamed_den_t h, float* xt, const float* mods, const int* lens, int nfe, int B, int T,
                                      void* ws, size_t ws_bytes, int use_graph, hipStream_t st) {
   return den_solve_lens(h, xt, mods, lens, nfe, B, T, ws, ws_bytes, use_graph, nullptr, st, "flamed_den_solve_lens");
+}
+
+FLAMED_API int flamed_den_lens_path(flamed_den_t h, int* path) {
+  Den* d = reinterpret_cast<Den*>(h);
+  FL_REQUIRE(d && path, "flamed_den_lens_path: bad args");
+  std::lock_guard<std::recursive_mutex> lk(d->mu);
+  *path = d->lens_path;
+  return kOk;
 }
 
 FLAMED_API int flamed_den_solve_rk2_lens(flamed_den_t h, float* xt, const float* mods, const int* lens, int nsteps, double a,

@@ -132,6 +132,7 @@ HIP_DIAG_SIGNATURES = {
                                        ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "flamed_den_chain_info": (c_int, [P, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "flamed_den_chain_busy": (c_int, [P, ctypes.POINTER(c_int)]),
+    "flamed_den_lens_path": (c_int, [P, ctypes.POINTER(c_int)]),
 }
 
 FLAMED_F32, FLAMED_BF16, FLAMED_FP8 = 0, 1, 2

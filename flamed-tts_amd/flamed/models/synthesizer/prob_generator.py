@@ -575,6 +575,14 @@ class DenoiserHIP:
             return runs.value, bool(broken.value), float(ms.value)
         return runs.value, bool(broken.value)
 
+    def lens_path(self) -> int:
+        """How this handle's last exact-lengths solve (solve / solve_rk2 with lens) ran (flamed_den_lens_path): 0 the
+        dense solve, 1 one persistent launch, 2 one ragged batch on the launch path, 3 one utterance after another;
+        -1 before the first."""
+        path = ctypes.c_int(-1)
+        nat.check(nat.lib().flamed_den_lens_path(self.handle, ctypes.byref(path)), "flamed_den_lens_path")
+        return path.value
+
     def persist_fails(self) -> int:
         """Failed (NaN-poisoned) persistent launches so far on this handle (diagnostic: waits for the device)."""
         f = ctypes.c_int(0)
@@ -595,7 +603,7 @@ class DenoiserHIP:
         checked later (settle), and a failed one re-written in place before the caller's next sync point.
 
         lens (B ints, 2 <= lens[u] <= T): exact lengths (flamed_den_solve_lens) -- utterance u is solved over
-        xt[u, :lens[u]] alone, the frames behind it are never read (they may hold anything) and come out 0."""
+        xt[u, :lens[u]] alone, the frames behind it never influence it (they may hold anything) and come out 0."""
         return self._solve(xt, ts, spk, nfe, None, lens)
 
     def solve_rk2(self, xt: torch.Tensor, ts_eval: torch.Tensor, spk: torch.Tensor, nsteps: int, a: float,
@@ -692,7 +700,7 @@ class DenoiserHIP:
                     "tidx": (r // B).to(torch.int32), "sidx": (r % B).to(torch.int32)}
             self._solve_bufs = {key: bufs}
         nbytes = L.flamed_den_workspace_size(self.handle, B, T)
-        if lens is not None:  # (an ineligible batch solves one utterance after another in the same workspace)
+        if lens is not None:  # (fp8 handles and knob ragged_launch 0 solve one utterance after another in the same workspace)
             nbytes = max([nbytes] + [L.flamed_den_workspace_size(self.handle, 1, n) for n in set(lens)])
         ws = self.ws.get(nbytes, dev)
         if "mods" not in bufs:

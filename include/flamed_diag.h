@@ -98,6 +98,10 @@ FLAMED_API int flamed_den_chain_info(flamed_den_t h, int* parked, int* retries);
 /* ... and how many probe pairs were inconclusive (neither concurrent nor dispatched back-to-back: the device was busy);
  * those never park a stream. */
 FLAMED_API int flamed_den_chain_busy(flamed_den_t h, int* busy);
+/* How this handle's last flamed_den_solve_lens / _solve_rk2_lens ran: *path = 0 the dense solve (every length T, or one
+ * utterance), 1 one persistent launch, 2 one ragged batch on the launch path, 3 one utterance after another; -1 before
+ * the first such call. */
+FLAMED_API int flamed_den_lens_path(flamed_den_t h, int* path);
 
 #ifdef __cplusplus
 }

@@ -122,14 +122,21 @@ FLAMED_API int flamed_den_solve_rk2(flamed_den_t h, float* xt, const float* mods
 /* Exact lengths: the same solves for a padded ragged batch.  lens: B HOST ints, 2 <= lens[u] <= T.  Utterance u (rows
  * u T .. u T + lens[u] - 1 of xt, modulation row u of every block) is solved over its own lens[u] frames, exactly as
  * if it were alone at T = lens[u]: GroupNorm over lens[u] frames, the depthwise and conv_out zero padding at its own
- * end.  Rows u T + lens[u] .. (u + 1) T - 1 of xt are neither read nor written (the caller zeroes or ignores them).
+ * end.  Rows u T + lens[u] .. (u + 1) T - 1 of xt (the padding rows) never influence a valid row and are never written;
+ * they may be read (row-local kernels compute them for nobody), so they must be addressable but may hold anything, NaN
+ * included (the caller zeroes or ignores them afterwards).
  * Every length equal to T gives bitwise flamed_den_solve / _solve_rk2.  2..8 utterances that are eligible for the
  * persistent solve below run as ONE persistent launch (its exact-lengths variants, same failure semantics: the valid
- * rows are NaN-poisoned); everything else (fp32 / fp8 handles, B > 8, B x T > 4096, "persist" 0, use_graph bit 2, a
- * refused cooperative grid) solves one utterance after another on plain launches.  ws as for (B, T), and at least
- * flamed_den_workspace_size(h, 1, lens[u]) for every u.  A null pointer or a length outside 2..T returns 1001 with a
- * flamed_last_error text before any pointer is touched (one frame alone is what the reference's GroupNorm over T
- * refuses); flamed_den_solve_rk2's checks of nsteps and a apply unchanged. */
+ * rows are NaN-poisoned).  Everything else (fp32 handles, B > 8, B x T > 4096, "persist" 0, use_graph bit 2, a refused
+ * cooperative grid) runs the ragged batch on the launch path in one call: the solve flamed_den_solve would run for
+ * (B, T) -- graph of launches (use_graph bit 1; the graph holds the address of the handle's device copy of lens, not
+ * the lengths), fused Euler steps, sub-batch chains, RK2 -- with the depthwise conv + GroupNorm, the conv_out taps
+ * and the state update ended at every utterance's own length.  fp8 handles, and every handle under flamed_tune
+ * "ragged_launch" 0 (default 1; an A/B knob), solve one utterance after another on plain launches.  ws as for (B, T);
+ * the one-after-another path needs at least flamed_den_workspace_size(h, 1, lens[u]) for every u as well.  A null
+ * pointer or a length outside 2..T returns 1001 with a flamed_last_error text before any pointer is touched (one
+ * frame alone is what the reference's GroupNorm over T refuses); flamed_den_solve_rk2's checks of nsteps and a apply
+ * unchanged. */
 FLAMED_API int flamed_den_solve_lens(flamed_den_t h, float* xt, const float* mods, const int* lens, int nfe, int B, int T,
                                      void* ws, size_t ws_bytes, int use_graph, hipStream_t stream);
 FLAMED_API int flamed_den_solve_rk2_lens(flamed_den_t h, float* xt, const float* mods, const int* lens, int nsteps, double a,
@@ -247,6 +254,8 @@ FLAMED_API int flamed_den_time_kernels_graph(flamed_den_t h, float* xt, const fl
  *   "split_batch"   — large-M bf16 solves as this many concurrent sub-batch chains (parallel graph
  *                     branches; default 2, bitwise equal to 1 = one chain);
  *   "split_min_rows"— ... only when every chain keeps at least this many rows (default 6144);
+ *   "ragged_launch" — 1 (default): an exact-lengths batch (flamed_den_solve_lens) that the persistent kernel cannot take
+ *                     runs as one ragged batch on the launch path; 0: one utterance after another (A/B, fallback);
  *   "split_graph"   — 0 (default): one graph per chain, chains 1.. replayed on priority streams of their
  *                     own; 1: one graph with the chains as parallel branches (round 4);
  *   "split_prio"    — split chains' replay streams: 0 (default) chain 0 on the caller's stream, chain 1
