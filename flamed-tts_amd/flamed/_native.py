@@ -69,6 +69,8 @@ SIGNATURES = {
     "flamed_lr_lengths": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P]),
     "flamed_lr_lengths_exact": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P]),
     "flamed_lr_expand": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P]),
+    "flamed_noise_state": (c_int, [P, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(c_int), c_int, c_float, c_int, c_int,
+                                   c_int, P, P]),
     "flamed_fac_create": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int), c_int, ctypes.POINTER(P)]),
     "flamed_fac_destroy": (c_int, [P]),
     "flamed_fac_num_weights": (c_int, [P]),
@@ -133,6 +135,7 @@ HIP_DIAG_SIGNATURES = {
     "flamed_den_chain_info": (c_int, [P, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "flamed_den_chain_busy": (c_int, [P, ctypes.POINTER(c_int)]),
     "flamed_den_lens_path": (c_int, [P, ctypes.POINTER(c_int)]),
+    "flamed_noise_bits": (c_int, [ctypes.c_ulonglong, c_int, ctypes.c_ulonglong, c_int, P, P]),
 }
 
 FLAMED_F32, FLAMED_BF16, FLAMED_FP8 = 0, 1, 2

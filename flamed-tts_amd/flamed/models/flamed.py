@@ -26,6 +26,7 @@ import torch.nn.functional as F
 from flamed.text import text_to_sequence
 from flamed.models.synthesizer.prior_generator import PriorGenerator
 from flamed.models.synthesizer.prob_generator import ProbGenerator
+from flamed.utils.noise import utterance_seed
 
 
 class Flamed(nn.Module):
@@ -72,11 +73,14 @@ class Flamed(nn.Module):
                timbre: torch.Tensor = None, sr: int = 16000, codec_cfg=None, codec_encoder=None, codec_decoder=None,
                temp_durgen: float = 0.3, temp_denoiser: float = 0.3, nsteps_durgen: int = 64,
                nsteps_denoiser: int = 64, lexicon_path: str = None, cleaners=("english_cleaners",),
-               solver_denoiser: str = "euler", exact_lengths: bool = False, exact_prior: bool = False):
+               solver_denoiser: str = "euler", exact_lengths: bool = False, exact_prior: bool = False, seed: int = None,
+               seed_index: int = 0):
         """reference :89-166 (same argument validation and ValueErrors).  solver_denoiser: the denoiser's ODE
         solver ("euler", the reference's; "midpoint" / "heun": second order, nsteps_denoiser then counts velocity
         evaluations and must be even -- ProbGenerator.sample).  exact_lengths: as in sample_batch (one utterance has
-        no padding, so it changes nothing here); exact_prior likewise."""
+        no padding, so it changes nothing here); exact_prior likewise.  seed (opt-in; None draws from the global RNG as
+        the reference does): keyed noise, the utterance gets sample_batch(seeds=[utterance_seed(seed, seed_index)]) --
+        index 0 unless the caller numbers its utterances (flamed.utils.noise)."""
         if codec_decoder is None or (codec_encoder is None and prompt_raw is not None):
             if codec_cfg is None:
                 raise ValueError("The codec_encoder or codec_decoder is set to None. To initialize the codec encoder or "
@@ -113,7 +117,8 @@ class Flamed(nn.Module):
                                 prompts=prompts, timbres=timbre, codec_decoder=codec_decoder, temp_durgen=temp_durgen,
                                 temp_denoiser=temp_denoiser, nsteps_durgen=nsteps_durgen,
                                 nsteps_denoiser=nsteps_denoiser, solver_denoiser=solver_denoiser,
-                                exact_lengths=exact_lengths, exact_prior=exact_prior)
+                                exact_lengths=exact_lengths, exact_prior=exact_prior,
+                                **({} if seed is None else {"seeds": [utterance_seed(seed, seed_index)]}))
         wav = out["wav"][0][0].detach().cpu().numpy()
         return {"wav": wav, "time": time.time() - start}
 
@@ -121,8 +126,12 @@ class Flamed(nn.Module):
     def sample_batch(self, phonemes, src_lens, prompts, timbres, codec_decoder=None, temp_durgen: float = 0.3,
                      temp_denoiser: float = 0.3, nsteps_durgen: int = 64, nsteps_denoiser: int = 64,
                      solver_denoiser: str = "euler", exact_lengths: bool = False, exact_prior: bool = False,
-                     prompt_lens=None):
-        """reference :168-217; solver_denoiser as in sample.  exact_lengths (opt-in): every utterance of the padded
+                     prompt_lens=None, seeds=None):
+        """reference :168-217; solver_denoiser as in sample.  seeds (opt-in; None draws every noise tensor from the
+        global CPU RNG as the reference does): B ints in [0, 2^64), one per utterance (utterance_seeds(seed, indices));
+        both stages then take keyed noise (PVA.flow, ProbGenerator.sample), utterance u's draws depend on seeds[u]
+        alone, and with exact_lengths and exact_prior its waveform depends on nothing else of the batch.
+        exact_lengths (opt-in): every utterance of the padded
         batch gets the latents it would get alone -- its condition fold and its solve run over its own frames only
         and its padding frames are 0 (ProbGenerator.sample), and the FaCodec decode gets lens = (~tgt_mask).sum(-1), so
         wav[u, :, :wav_lens[u]] is the waveform utterance u would get alone and wav[u, :, wav_lens[u]:] is exactly 0
@@ -138,20 +147,25 @@ class Flamed(nn.Module):
         start = time.time()
         dev = self.device
         phonemes, src_lens, prompts, timbres = phonemes.to(dev), src_lens.to(dev), prompts.to(dev), timbres.to(dev)
+        skw = {}
+        if seeds is not None:
+            skw["seeds"] = [int(s) for s in seeds]
+            if len(skw["seeds"]) != phonemes.size(0):
+                raise ValueError(f"seeds must hold one seed per utterance ({len(skw['seeds'])} for {phonemes.size(0)})")
         if exact_prior or prompt_lens is not None:
             if prompt_lens is None:
                 prompt_lens = self._prompt_lens_from_pad(prompts)
             prior_emb_cond, prior_logits, tgt_mask = self.prior_generator.sample(
                 texts=phonemes, src_lens=src_lens, max_src_len=phonemes.size(-1), prompts=prompts,
                 prompts_len=prompts.size(-1), nfe=nsteps_durgen, temperature=temp_durgen,
-                exact_lengths=bool(exact_prior), prompt_lens=prompt_lens)
+                exact_lengths=bool(exact_prior), prompt_lens=prompt_lens, **skw)
         else:
             prior_emb_cond, prior_logits, tgt_mask = self.prior_generator.sample(
                 texts=phonemes, src_lens=src_lens, max_src_len=phonemes.size(-1), prompts=prompts,
-                prompts_len=prompts.size(-1), nfe=nsteps_durgen, temperature=temp_durgen)
+                prompts_len=prompts.size(-1), nfe=nsteps_durgen, temperature=temp_durgen, **skw)
         latents = self.prob_generator.sample(cond=prior_emb_cond, spk=timbres, nfe=nsteps_denoiser,
                                              temperature=temp_denoiser, mask=~tgt_mask.unsqueeze(-1),
-                                             solver=solver_denoiser, exact_lengths=exact_lengths)
+                                             solver=solver_denoiser, exact_lengths=exact_lengths, **skw)
         if latents.is_cuda:
             torch.cuda.synchronize(latents.device)  # 'time' covers the device work, as the eager reference does
             den = self.prob_generator.denoiser

@@ -131,19 +131,21 @@ class PriorGenerator(nn.Module):
         return embs, logits, tgt_masks
 
     def sample(self, texts, src_lens, max_src_len, prompts, prompts_len, nfe=4, temperature=1.0, exact_lengths=False,
-               prompt_lens=None):
+               prompt_lens=None, seeds=None):
         """reference :141-196 -> (prior embeddings (B,Q,T,D), logits (B,V+1,Q,T), tgt mask (B,T)).
         exact_lengths (opt-in, no reference counterpart): every utterance of the padded batch gets the durations, the
         frame count, the prior embeddings and the logits it would get alone, from its own slice of the same noise
         draws (PVA.flow / LengthRegulator.LR with exact=True); everything behind an utterance's end is 0.
         prompt_lens (B ints, 0 <= prompt_lens[u] <= prompts_len; None = prompts_len for all): utterance u's prompt is
         prompts[u, :, :prompt_lens[u]]; the decoders then see its own prompt only and place target frame t at
-        position prompt_lens[u] + t."""
+        position prompt_lens[u] + t.
+        seeds (opt-in; B ints in [0, 2^64)): the duration and silence noise is keyed per utterance instead of drawn
+        from the global RNG (PVA.flow)."""
         src_masks = get_mask_from_lengths(src_lens, max_src_len)
         hip = self._use_hip(texts)
         output = ops.prior_encode(self.hip().oid, texts, src_masks) if hip else self.encoder(texts, src_masks)
         if not exact_lengths and prompt_lens is None:
-            output, tgt_lens = self.pva.sample(output, src_lens, src_masks, nfe=nfe, temperature=temperature)
+            output, tgt_lens = self.pva.sample(output, src_lens, src_masks, nfe=nfe, temperature=temperature, seeds=seeds)
             tgt_masks = get_mask_from_lengths(tgt_lens, output.size(1))
             if hip:
                 embs, logits = ops.prior_decode(self.hip().oid, output, tgt_masks, prompts, int(prompts_len))
@@ -154,7 +156,7 @@ class PriorGenerator(nn.Module):
         if len(plens) != texts.size(0) or any(n < 0 or n > P for n in plens):
             raise ValueError(f"prompt_lens must hold one length in [0, {P}] per utterance (got {plens})")
         output, tgt_lens = self.pva.sample(output, src_lens, src_masks, nfe=nfe, temperature=temperature,
-                                           exact=bool(exact_lengths))
+                                           exact=bool(exact_lengths), seeds=seeds)
         tgt_masks = get_mask_from_lengths(tgt_lens, output.size(1))
         if hip:
             embs, logits = ops.prior_decode_lens(self.hip().oid, output, tgt_masks, prompts, P, plens)

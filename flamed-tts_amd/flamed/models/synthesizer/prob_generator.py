@@ -4,7 +4,7 @@ flamed/models/synthesizer/prob_generator.py).
 Module/parameter names match the reference state dict exactly
 (e.g. `denoiser.res_blocks.{i}.adaLN_modulation.1.weight`), and the public signatures are kept:
   * SimpleMLPAdaLN.forward(x, t, c)                       (reference :349-365)
-  * ProbGenerator.sample(cond, spk, mask, nfe, temperature) (reference :434-447)
+  * ProbGenerator.sample(cond, spk, mask, nfe, temperature) (reference :434-447; seeds=: keyed per-utterance noise)
   * ProbGenerator.compute_loss(x1, cond, spk, mask)         (reference :414-432)
 
 Execution: on a CUDA (ROCm) device at inference time the denoiser and the whole Euler loop run in
@@ -28,6 +28,7 @@ import torch.nn.functional as F
 from flamed import _native as nat
 from flamed import ops
 from flamed.utils.conv import GemmConv1d
+from flamed.utils.noise import STREAM_LATENT, noise_state
 
 
 # ODE solvers of ProbGenerator.sample: name -> stage parameter a of the two-stage second-order family
@@ -359,9 +360,15 @@ class ProbGenerator(nn.Module):
         x1_est = (xt + (1 - k * t) * vt) * mask
         return {"fm_loss": F.mse_loss(vt, dx), "anchor_loss": F.mse_loss(x1_est, x1)}
 
-    def sample(self, cond, spk, mask, nfe=4, temperature=1.0, solver="euler", exact_lengths=False):
+    def sample(self, cond, spk, mask, nfe=4, temperature=1.0, solver="euler", exact_lengths=False, seeds=None):
         """reference :434-447.  Noise is drawn from the global CPU RNG with the reference's shape and
         order, so seeded runs reproduce the reference trajectory.
+
+        seeds (opt-in; None is the draw above, bit for bit): B ints in [0, 2^64), one per utterance.  The initial state
+        is then flamed.utils.noise.noise_state(folded cond, seeds, lens if exact_lengths else None, temperature, 0):
+        keyed noise indexed by (frame, channel) inside the utterance, so utterance u's noise depends on seeds[u] alone
+        -- not on its place in the batch, the padded length or the batch size -- and the global RNG is not touched.
+        With exact_lengths an utterance's latents then depend on nothing but its own inputs and its seed.
 
         exact_lengths (opt-in; the default is the reference's padded batch, bit for bit): utterance u of the padded
         batch, len_u frames by its (prefix) mask, is folded and solved over those frames alone -- exactly what it gets
@@ -385,7 +392,10 @@ class ProbGenerator(nn.Module):
                 check_groupnorm_frames(1, n, self.denoiser.model_channels)
         cond = self.fold_condition(cond, mask, exact=True) if exact_lengths else self.fold_condition(cond, mask)
         b, l, _ = cond.shape
-        xt = torch.randn((b, l, self.target_dim)).to(cond.device) * temperature + cond
+        if seeds is None:
+            xt = torch.randn((b, l, self.target_dim)).to(cond.device) * temperature + cond
+        else:
+            xt = noise_state(cond, seeds, lens, temperature, STREAM_LATENT)
         if a is None:
             ts = torch.linspace(0, 1, nfe + 1, device=cond.device)
             if self.denoiser._use_hip(xt):

@@ -21,6 +21,7 @@ import torch.nn.functional as F
 
 from flamed import _native as nat
 from flamed import ops
+from flamed.utils.noise import STREAM_DURATION, STREAM_SILENCE, noise_state
 from flamed.utils.tools import pad
 
 
@@ -208,19 +209,28 @@ class PVA(nn.Module):
         x, _ = self.length_regulator(x, phone_duration, sil_duration, src_len, max_tgt_len)
         return x, losses
 
-    def flow(self, x, src_mask, nfe, temperature, exact=False):
+    def flow(self, x, src_mask, nfe, temperature, exact=False, seeds=None):
         """Euler loop of both generators (pva.py:97-109); returns final log-durations (dur, sil).
         Noise: dur then sil from the global CPU RNG, as the reference draws it.
+        seeds (opt-in; None is that draw, bit for bit): B ints in [0, 2^64); the two states are then keyed noise over
+        the phoneme axis (flamed.utils.noise.noise_state, stream 1 for dur and 2 for sil, with the lengths in the exact
+        mode), so utterance u's draws depend on seeds[u] alone and the global RNG is not touched.
         exact (opt-in, no reference counterpart): utterance u of the padded batch, len_u = its count of unmasked
         phonemes (src_mask is a prefix mask), is flowed as if alone -- over x[u, :len_u] with no mask, from its own
         slice of the same two draws -- and the returned states are exactly 0 on [len_u, L).  The reference's padded
         flow lets the two k3 convolutions read the padded rows, whose state stays noise * temperature."""
         b, l, _ = x.size()
         ts = torch.linspace(0, 1, nfe + 1, device=x.device)
-        dur_t = torch.randn((b, l)).to(x.device) * temperature
-        sil_t = torch.randn((b, l)).to(x.device) * temperature
+        lens = None
+        if seeds is None:
+            dur_t = torch.randn((b, l)).to(x.device) * temperature
+            sil_t = torch.randn((b, l)).to(x.device) * temperature
         if exact:
             lens = [int(n) for n in (~src_mask.bool()).sum(-1).tolist()]
+        if seeds is not None:
+            dur_t, sil_t = (noise_state(None, seeds, lens, temperature, sid, shape=(b, l, 1), device=x.device).reshape(b, l)
+                            for sid in (STREAM_DURATION, STREAM_SILENCE))
+        if exact:
             if _hip_ok(x, self):
                 return ops.pva_flow_exact(self.hip().oid, x, dur_t, sil_t, ts, nfe, lens)
             return self._flow_each_alone(x, dur_t, sil_t, ts, nfe, lens)
@@ -244,10 +254,10 @@ class PVA(nn.Module):
             dur_o[u, :n], sil_o[u, :n] = d[0], s[0]
         return dur_o, sil_o
 
-    def sample(self, x, src_len, src_mask, max_tgt_len=None, nfe=32, temperature=1.0, exact=False):
+    def sample(self, x, src_len, src_mask, max_tgt_len=None, nfe=32, temperature=1.0, exact=False, seeds=None):
         """reference pva.py:88-116; exact: flow and LengthRegulator.LR with exact lengths (every utterance's durations
-        and frame count as if alone)."""
-        dur_t, sil_t = self.flow(x, src_mask, nfe, temperature, exact=exact)
+        and frame count as if alone); seeds: keyed per-utterance noise (flow)."""
+        dur_t, sil_t = self.flow(x, src_mask, nfe, temperature, exact=exact, seeds=seeds)
         if _lr_hip_ok(x):
             return self.length_regulator.LR(x, dur_t, sil_t, src_len, max_tgt_len, log_domain=True, exact=exact)
         phone_duration = torch.clamp(torch.round(torch.exp(dur_t) - 1), min=0)

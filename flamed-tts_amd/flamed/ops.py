@@ -32,6 +32,9 @@ take tensors and scalars only); the registry holds weak references, so a dropped
                                                    frames, as if alone (position row pe[0] for every utterance)
   flamed_hip::prior_encode(id, texts, mask)        Encoder.forward (prior)         prior_generator.py:152-153
   flamed_hip::prior_decode(id, x, mask, prompts, P) bridge + decoders + head       prior_generator.py:165-188
+  flamed_hip::noise_state(cond, seeds, lens, temperature, stream_id, B, T, C, device)  keyed noise (no reference
+                                                   counterpart; opt-in): cond + temperature * n, n counter-based
+                                                   normals keyed per utterance (flamed/utils/noise.py), 0 behind lens
 
 None of the ops has an autograd formula: the modules route autograd (training) to their torch ops
 before reaching here, exactly as the reference trains.  There is no CPU kernel: the ops are registered
@@ -42,7 +45,7 @@ from __future__ import annotations
 import itertools
 import threading
 import weakref
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -310,6 +313,22 @@ def _(oid, x, tgt_mask, prompts, prompts_len, prompt_lens):
     return x.new_empty((B, nq, T, D)), x.new_empty((B, V1, nq, T))
 
 
+# ---------------------------------------------------------------- keyed noise
+
+@torch.library.custom_op("flamed_hip::noise_state", mutates_args=())
+def noise_state(cond: Optional[Tensor], seeds: List[int], lens: Optional[List[int]], temperature: float, stream_id: int,
+                B: int, T: int, C: int, device: torch.device) -> Tensor:
+    # (a schema int is signed 64-bit: seeds travel as their two's-complement images)
+    from .utils.noise import hip_noise_state
+    return hip_noise_state(cond, [s & 0xFFFFFFFFFFFFFFFF for s in seeds], lens, temperature, stream_id, (B, T, C), device)
+
+
+@noise_state.register_fake
+def _(cond, seeds, lens, temperature, stream_id, B, T, C, device):
+    return torch.empty((B, T, C), dtype=torch.float32, device=device)
+
+
+# the ops the model modules call themselves (noise_state is reached through flamed.utils.noise.noise_state)
 OPS = ("den_velocity", "den_solve", "den_solve_rk2", "den_solve_lens", "den_solve_rk2_lens", "cond_fold", "cond_fold_exact",
        "pva_flow", "length_regulate", "fac_decode", "fac_decode_lens", "enc_encode", "vq_encode", "prior_encode", "prior_decode",
        "pva_flow_exact", "length_regulate_exact", "prior_decode_lens", "enc_encode_lens", "vq_encode_lens")

@@ -18,7 +18,9 @@ collective, only the timing records are gathered for the RTF printed by rank 0 (
 Additions (all optional; the reference's invocations behave the same):
   * `--codec-ckpt-dir DIR` — where ns3_facodec_{encoder,decoder}.bin live (reference: fixed path under
     flamed/models/facodec/checkpoints, :72-73);
-  * a second summary line with latent frames/s over the measured sample time.
+  * a second summary line with latent frames/s over the measured sample time;
+  * `--noise utterance --seed S` — keyed noise (flamed/utils/noise.py): utterance i draws from utterance_seed(S, i),
+    so a file does not change with the batch it shares, --batch-size, --skip-existing or the number of GPUs.
 Config files are read with yaml.safe_load (omegaconf is not installed); checkpoints with
 torch.load(weights_only=True) only.  `python -m flamed.utils.random_ckpt --out-dir D` writes a seeded
 random-init checkpoint + config + codec weights (BASELINE config 0).
@@ -41,6 +43,7 @@ from flamed import Flamed  # noqa: E402
 from flamed.models.facodec import FACodecEncoder, FACodecDecoder  # noqa: E402
 from flamed.utils import dist as fdist  # noqa: E402
 from flamed.utils.audio import load_wav, write_wav  # noqa: E402
+from flamed.utils.noise import utterance_seeds  # noqa: E402
 
 SR = 16000
 HOP = 200  # FaCodec samples per latent frame
@@ -209,9 +212,9 @@ class RtfMeter:
         return sum(d * SR / HOP for d in self.durations) / total if total > 0 else float("nan")
 
 
-def _solver_suffix(solver_denoiser: str, exact_lengths: bool = False, exact_prior: bool = False) -> str:
+def _solver_suffix(solver_denoiser: str, exact_lengths: bool = False, exact_prior: bool = False, noise_seed=None) -> str:
     return (("" if solver_denoiser == "euler" else f"-{solver_denoiser}") + ("-exact" if exact_lengths else "") +
-            ("-xprior" if exact_prior else ""))
+            ("-xprior" if exact_prior else "") + ("" if noise_seed is None else f"-seed{noise_seed}"))
 
 
 def _prior_kw(exact_prior: bool) -> dict:
@@ -222,21 +225,25 @@ def _prior_kw(exact_prior: bool) -> dict:
 def synthesize_with_prompts(model: Flamed, codec_encoder, codec_decoder, text: str, prompt_dir: str,
                             prompt_list: List[str], output_dir: str, nsteps_durgen: int, nsteps_denoiser: int,
                             temp_durgen: float, temp_denoiser: float, meter: Optional[RtfMeter] = None,
-                            solver_denoiser: str = "euler", exact_lengths: bool = False, exact_prior: bool = False):
+                            solver_denoiser: str = "euler", exact_lengths: bool = False, exact_prior: bool = False,
+                            noise_seed: Optional[int] = None):
     """One `Flamed.sample` per prompt (reference :194-217).  A denoiser solver other than Euler is appended to the
-    output names, so runs with different solvers do not overwrite each other; so are `-exact` for exact lengths and `-xprior` for the exact prior stage."""
+    output names, so runs with different solvers do not overwrite each other; so are `-exact` for exact lengths and `-xprior` for the exact prior stage.
+    noise_seed (`--noise utterance --seed S`): prompt i of the list (its index before sharding) gets keyed noise under
+    utterance_seed(S, i), and `-seed{S}` is appended to the names."""
     os.makedirs(output_dir, exist_ok=True)
     meter = meter if meter is not None else RtfMeter()
     rank, world, _ = fdist.dist_env()
-    for prompt_name in _progress(fdist.shard(prompt_list, rank, world), desc="Synthesizing prompts"):
+    for index, prompt_name in _progress(fdist.shard(list(enumerate(prompt_list)), rank, world), desc="Synthesizing prompts"):
         audio_prompt = load_audio(_resolve_prompt_path(prompt_dir, prompt_name))
         res = model.sample(text=text, prompt_raw=audio_prompt, sr=SR, codec_encoder=codec_encoder,
                            codec_decoder=codec_decoder, nsteps_durgen=nsteps_durgen, nsteps_denoiser=nsteps_denoiser,
                            temp_durgen=temp_durgen, temp_denoiser=temp_denoiser, solver_denoiser=solver_denoiser,
-                           exact_lengths=exact_lengths, **_prior_kw(exact_prior))
+                           exact_lengths=exact_lengths, **_prior_kw(exact_prior),
+                           **({} if noise_seed is None else {"seed": noise_seed, "seed_index": index}))
         meter.add(res["time"], len(res["wav"]))
         stem = os.path.splitext(os.path.basename(prompt_name))[0]
-        out_name = f"{stem}-{nsteps_durgen}-{nsteps_denoiser}-{temp_durgen}-{temp_denoiser}{_solver_suffix(solver_denoiser, exact_lengths, exact_prior)}.wav"
+        out_name = f"{stem}-{nsteps_durgen}-{nsteps_denoiser}-{temp_durgen}-{temp_denoiser}{_solver_suffix(solver_denoiser, exact_lengths, exact_prior, noise_seed)}.wav"
         write_wav(os.path.join(output_dir, out_name), res["wav"], SR)
     return meter.rtf()
 
@@ -245,22 +252,26 @@ def synthesize_with_metadata(model: Flamed, codec_encoder, codec_decoder, metada
                              output_dir: str, nsteps_durgen: int, nsteps_denoiser: int, temp_durgen: float,
                              temp_denoiser: float, skip_existing: bool, batch_size: int,
                              meter: Optional[RtfMeter] = None, solver_denoiser: str = "euler",
-                             exact_lengths: bool = False, exact_prior: bool = False, batch_prompts: bool = False):
+                             exact_lengths: bool = False, exact_prior: bool = False, batch_prompts: bool = False,
+                             noise_seed: Optional[int] = None):
     """Batched `Flamed.sample_batch` over a `target|prompt|text` file (reference :220-303).  A denoiser solver
     other than Euler is appended to the target directory's name, and `-exact` for exact lengths (every utterance of
     a padded batch then gets the latents and the waveform it would get alone, and its file is trimmed to its own
     length, out["wav_lens"]; without the flag every file of a batch has the batch's padded length), and `-xprior` for
     the exact prior stage (durations, frame counts and prior embeddings as if alone; the prompts' own lengths are
     read from the pad id that build_metadata_batch pads them with).  batch_prompts: the uncached prompts of a batch
-    are encoded together with exact lengths (same file names: every prompt gets what it gets alone)."""
+    are encoded together with exact lengths (same file names: every prompt gets what it gets alone).
+    noise_seed (`--noise utterance --seed S`): every line gets keyed noise under utterance_seed(S, i), i its index among
+    the file's non-empty lines -- taken before --skip-existing, sharding and batching, so a line's noise depends on
+    neither -- and `-seed{S}` is appended to the directory's name."""
     with open(metadata_file, "r", encoding="utf-8") as fin:
         entries = [line.strip() for line in fin if line.strip()]
-    target_dir = os.path.join(output_dir, f"nfe{nsteps_denoiser}-temp{temp_denoiser}{_solver_suffix(solver_denoiser, exact_lengths, exact_prior)}")
+    target_dir = os.path.join(output_dir, f"nfe{nsteps_denoiser}-temp{temp_denoiser}{_solver_suffix(solver_denoiser, exact_lengths, exact_prior, noise_seed)}")
     os.makedirs(target_dir, exist_ok=True)
     meter = meter if meter is not None else RtfMeter()
     cache: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
     pending: List[Dict[str, str]] = []
-    for entry in entries:
+    for index, entry in enumerate(entries):
         try:
             filename, prompt_filename, transcript = entry.split("|", 2)
         except ValueError:
@@ -270,7 +281,7 @@ def synthesize_with_metadata(model: Flamed, codec_encoder, codec_decoder, metada
         if skip_existing and os.path.exists(out_path):
             continue
         pending.append({"filename": filename, "prompt_path": _resolve_prompt_path(prompt_dir, prompt_filename),
-                        "text": transcript, "out_path": out_path})
+                        "text": transcript, "out_path": out_path, "index": index})
     rank, world, _ = fdist.dist_env()
     if world > 1:  # length buckets: phoneme count is the utterance-length (T x nfe work) proxy
         costs = [int(model._preprocess_english(it["text"])[0].size(-1)) for it in pending]
@@ -284,7 +295,9 @@ def synthesize_with_metadata(model: Flamed, codec_encoder, codec_decoder, metada
         out = model.sample_batch(phonemes=phonemes, src_lens=src_lens, prompts=prompts, timbres=timbres,
                                  codec_decoder=codec_decoder, temp_durgen=temp_durgen, temp_denoiser=temp_denoiser,
                                  nsteps_durgen=nsteps_durgen, nsteps_denoiser=nsteps_denoiser,
-                                 solver_denoiser=solver_denoiser, exact_lengths=exact_lengths, **_prior_kw(exact_prior))
+                                 solver_denoiser=solver_denoiser, exact_lengths=exact_lengths, **_prior_kw(exact_prior),
+                                 **({} if noise_seed is None else
+                                    {"seeds": utterance_seeds(noise_seed, [it["index"] for it in batch])}))
         per_sample = out["time"] / len(batch)
         wav_lens = out["wav_lens"].tolist() if "wav_lens" in out else [None] * len(batch)
         for item, wav_t, n in zip(batch, out["wav"], wav_lens):
@@ -315,6 +328,12 @@ def _validate_args(args: argparse.Namespace):
             raise ValueError(f"Metadata file not found: {args.metadata_file}")
         if args.batch_size < 1:
             raise ValueError("--batch-size must be >= 1.")
+    if getattr(args, "noise", "global") == "utterance":
+        seed = getattr(args, "seed", None)
+        if seed is None:
+            raise ValueError("--noise utterance needs --seed.")
+        if not 0 <= seed < 1 << 64:
+            raise ValueError("--noise utterance needs a --seed in [0, 2^64).")
 
 
 def build_arg_parser():
@@ -357,6 +376,12 @@ def build_arg_parser():
                    help="Directory with ns3_facodec_{encoder,decoder}.bin (default: flamed/models/facodec/checkpoints).")
     p.add_argument("--seed", type=int, default=None,
                    help="Seed the global RNGs (rank r of a torchrun job uses seed + r); default: unseeded, as the reference.")
+    p.add_argument("--noise", type=str, default="global", choices=["global", "utterance"],
+                   help="global (default): every noise tensor is drawn from the global CPU RNG for the whole batch, as "
+                        "the reference does.  utterance (needs --seed S): keyed noise, utterance i -- its line among the "
+                        "metadata file's non-empty lines, or its place in --prompt-list -- draws from its own seed "
+                        "utterance_seed(S, i), whatever batch, --batch-size, --skip-existing state or GPU count it runs "
+                        "under (S is not offset by the rank); `-seed{S}` is appended to the output names.")
     return p
 
 
@@ -374,7 +399,8 @@ def main(args: Optional[argparse.Namespace] = None):
         raise
     device = resolve_device(args.device)
     distributed = fdist.init(device.type)
-    if getattr(args, "seed", None) is not None:
+    keyed = getattr(args, "noise", "global") == "utterance"
+    if getattr(args, "seed", None) is not None and not keyed:
         torch.manual_seed(fdist.rank_seed(args.seed))
     codec_encoder, codec_decoder = get_codec(device, getattr(args, "codec_ckpt_dir", None))
     model = prepare_model(args.cfg_path, args.ckpt_path, device, args.weights_only)
@@ -384,7 +410,8 @@ def main(args: Optional[argparse.Namespace] = None):
                   temp_durgen=args.temp_durgen, temp_denoiser=args.temp_denoiser, meter=meter,
                   solver_denoiser=getattr(args, "solver_denoiser", "euler"),
                   exact_lengths=bool(getattr(args, "exact_lengths", False)),
-                  exact_prior=bool(getattr(args, "exact_prior", False)))
+                  exact_prior=bool(getattr(args, "exact_prior", False)),
+                  **({"noise_seed": int(args.seed)} if keyed else {}))
     if args.metadata_file:
         rtf = synthesize_with_metadata(metadata_file=args.metadata_file, skip_existing=args.skip_existing,
                                        batch_size=args.batch_size, **common,

@@ -102,6 +102,11 @@ FLAMED_API int flamed_den_chain_busy(flamed_den_t h, int* busy);
  * utterance), 1 one persistent launch, 2 one ragged batch on the launch path, 3 one utterance after another; -1 before
  * the first such call. */
 FLAMED_API int flamed_den_lens_path(flamed_den_t h, int* path);
+/* The raw Philox4x32-10 words behind flamed_noise_state: out[i] (device, n uint32) = word e % 4 of block e / 4 for
+ * e = first_element + i, key `seed`, stream `stream_id`.  first_element reaches block indices >= 2^32 without that
+ * much memory. */
+FLAMED_API int flamed_noise_bits(unsigned long long seed, int stream_id, unsigned long long first_element, int n,
+                                 unsigned int* out, hipStream_t stream);
 
 #ifdef __cplusplus
 }

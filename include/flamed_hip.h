@@ -371,6 +371,21 @@ FLAMED_API int flamed_lr_lengths_exact(const float* phone, const float* sil, con
 FLAMED_API int flamed_lr_expand(const float* x, const int64_t* cum, int B, int L, int H, int T_out, float* out,
                                 hipStream_t stream);
 
+/* ==================================== Keyed noise ====================================
+ * Counter-based noise keyed per utterance (DESIGN.md "Keyed noise"; no reference counterpart: the reference draws
+ * torch.randn((B, T, C)) from the global CPU RNG).  Utterance u's element e = t C + c is lane e % 4 of Philox4x32-10
+ * with key (low, high 32 bits of seeds[u]) and counter (e / 4 low, e / 4 high, stream_id, 0), turned into a standard
+ * normal n by an fp32 Box-Muller on the word pairs (w0, w1), (w2, w3); then
+ *   x[u][t][c] = fmaf(temperature, n, cond[u][t][c])   (temperature * n with cond = NULL),   0 for t >= lens[u].
+ * So an element never depends on B, T or the utterance's place in the batch: a batch row equals the call made for
+ * that utterance alone, and a shorter length is a prefix of a longer one, bit for bit.
+ * seeds: B HOST 64-bit seeds; lens: B HOST ints, 1 <= lens[u] <= T, or NULL = T for all.  Both travel as kernel
+ * arguments, 64 utterances per launch, so the arrays are free on return.  Stateless: no handle, no allocation, no
+ * synchronisation; capturable.  cond, x: device fp32 (B, T, C), x may alias cond.  stream_id >= 0 separates the draws
+ * of one utterance (0 denoiser latent, 1 PVA duration, 2 PVA silence).  Bad arguments return 1001 before any HIP call. */
+FLAMED_API int flamed_noise_state(const float* cond, const unsigned long long* seeds, const int* lens, int stream_id,
+                                  float temperature, int B, int T, int C, float* x, hipStream_t stream);
+
 /* ================================ FaCodec decoder (inference) ================================
  * Replaces FACodecDecoder.inference (facodec.py:630-638) and its model stack (:398-415).
  * Weight order for flamed_fac_load (fp32 device tensors as in the decoder state dict):
