@@ -1829,24 +1829,26 @@ struct Den {
   bool tune_own = false;    // set by flamed_den_tune: this handle keeps its own knobs
   int tune_ver = 0;         // bumped on every change of `tune` (graph cache key)
   int part_epoch = -1;      // tune_ver pinned by the s0 == 0 part of a flamed_den_solve_part sequence
-  // graph cache
-  hipGraphExec_t gexec = nullptr;
-  hipStream_t cap_stream = nullptr;
   static constexpr int kMaxSplit = 4;          // sub-batch chains of a large-M solve (den_split)
-  hipStream_t cap_aux[kMaxSplit] = {};         // (unused since round 5: each chain is captured on cap_stream)
-  hipEvent_t cap_ev[kMaxSplit] = {};           // fork / join events of the chains' replays
-  hipGraphExec_t gexec_c[kMaxSplit] = {};      // graphs of chains 1..S-1 (chain 0's is gexec)
+  // The cached graphs of the last solve on the graph of launches (den_solve_range): one exec per chain (exec[0] alone
+  // for one chain, or for tune split_graph 1), captured again when the key -- everything the captured launches bake
+  // in -- changes.
+  struct SolveGraphs {
+    hipGraphExec_t exec[kMaxSplit] = {};
+    std::vector<const void*> key;
+    bool hit(const std::vector<const void*>& k) const { return exec[0] && key == k; }
+    void retire() { for (auto& g : exec) retire_graph(g); key.clear(); }
+  } graphs;
+  hipStream_t cap_stream = nullptr;
+  hipStream_t cap_aux[kMaxSplit] = {};         // tune split_graph 1: capture streams of the branches of chains 1..S-1
+  hipEvent_t cap_ev[kMaxSplit] = {};           // fork / join events of the chains' captures and replays
   hipStream_t run_aux[3][kMaxSplit] = {};      // replay streams of the chains per tune split_prio (den_chain_streams)
   static constexpr int kMaxParked = 8;
   hipStream_t parked[kMaxParked] = {};         // streams the queue probe found serialising with a chain's (kept alive)
   int n_parked = 0, qprobe_retries = 0;
   int qprobe_busy = 0;  // probe pairs that neither ran concurrently nor back-to-back (the device was busy): not parked
   int* qprobe = nullptr;                       // probe flag + result words
-  int g_B = -1, g_T = -1, g_nfe = -1, g_epoch = -1;
-  double g_a = 0.0;  // stage parameter of the cached graph's solver (0: Euler)
-  const void *g_xt = nullptr, *g_mods = nullptr, *g_ws = nullptr;
-  const int* g_lens = nullptr;  // ... and its lengths array (exact lengths; null: a dense solve's graph)
-  DevLens dlens;               // device copy of an exact-lengths call's lengths (launch path), filled in stream order per call
+  DevLens dlens;              // device copy of an exact-lengths call's lengths (launch path), filled in stream order per call
   int lens_path = -1;          // how the last _lens solve ran (flamed_den_lens_path)
   int* ctr = nullptr;  // device Euler step counter for graph replay
   int* scnt = nullptr;  // split-K tile counters (zeroed at load; every launch leaves them zero)
@@ -1892,6 +1894,28 @@ static void persist_release(Den* d) {
   d->pring_n = 0;
 }
 static int persist_alloc(Den* d, hipStream_t st);
+
+// Drops every device-side resource of a handle and nulls its field (handle destroy / re-load on another device); the
+// caller holds the handle's lock with the handle's device current.
+static void den_release_device(Den* d) {
+  auto drop_stream = [](hipStream_t& s) { if (s) (void)hipStreamDestroy(s); s = nullptr; };
+  auto drop_mem = [](auto*& p) { if (p) (void)hipFree(p); p = nullptr; };
+  d->graphs.retire();
+  drop_stream(d->cap_stream);
+  for (auto& a : d->cap_aux) drop_stream(a);
+  for (auto& r : d->run_aux)
+    for (auto& a : r) drop_stream(a);
+  for (int i = 0; i < d->n_parked; ++i) drop_stream(d->parked[i]);
+  d->n_parked = 0;
+  drop_mem(d->qprobe);
+  for (auto& e : d->cap_ev)
+    if (e) { (void)hipEventDestroy(e); e = nullptr; }
+  drop_mem(d->ctr); drop_mem(d->scnt); drop_mem(d->gcnt);
+  d->dlens.release();
+  persist_release(d);
+  drop_mem(d->dev);
+  d->pdev_ok = -1;
+}
 
 // Active knobs of a handle call: the process defaults (re-snapshotted when flamed_tune moved the epoch)
 // unless flamed_den_tune gave the handle its own.
@@ -1992,7 +2016,8 @@ static size_t den_ws_bytes(const Den* d, int B, int T) { return den_ws_layout(d,
 
 // Large-M solves as concurrent sub-batches (tune split_batch, default 2): utterances are independent in the
 // denoiser (GroupNorm statistics and the depthwise halo never cross an utterance: prob_generator.py:81-89),
-// so the batch's Euler steps run as S chains of B / S utterances, captured as S parallel branches of one graph.
+// so the batch's Euler steps run as S chains of B / S utterances, each captured as a graph of its own and replayed on
+// a stream of its own (den_chain_streams; tune split_graph 1: the chains as S parallel branches of one graph).
 // One chain's inter-kernel gaps and the partly filled last round of its GEMM tiles are then covered by the
 // other chain's kernels (B = 64: 336 -> 295 ms, B = 32: 189 -> 159 ms; S = 4: 307 / 189).  The chains are
 // bitwise equal to the single chain (test_cfg2_split_batch_bitwise) since dwgn's pair math is scalar (dg_fma:
@@ -2014,6 +2039,41 @@ static size_t den_solve_ws(const Den* d, int B, int T) {
   const size_t split = S > 1 ? (size_t)S * den_split_ws(d, B, T, S) : 0;
   return one > split ? one : split;
 }
+
+// Chain k of the S sub-batch chains of a B x T solve: what of the solve is the chain's own.  The whole batch (S = 1,
+// and every single step or velocity call) is chain 0 of 1.
+struct DenChain {
+  float* x;           // state rows, Bk T x C
+  const float* mods;  // modulation row of its first utterance in row block 0 of the table
+  DenWs w;            // its workspace, laid out once
+  const int* lens;    // its slice of the lengths array (exact lengths; null = dense)
+  int* ctr;           // its step-counter word (graph replay)
+  int Bk, T;          // its utterances
+  int Bs;             // utterances per row block of the table (the whole batch)
+  int chain, nchains;
+};
+static DenChain den_chain(const Den* d, float* xt, const float* mods, void* ws, int B, int T, int S, const int* dlens, int k) {
+  DenChain c;
+  c.Bk = B / S; c.T = T; c.Bs = B; c.chain = k; c.nchains = S;
+  c.x = xt + (size_t)k * c.Bk * T * d->C;
+  c.mods = mods + (size_t)k * c.Bk * d->MS;
+  den_ws_layout(d, c.Bk, T, static_cast<char*>(ws) + (S > 1 ? k * den_split_ws(d, B, T, S) : 0), &c.w);
+  c.lens = dlens ? dlens + (size_t)k * c.Bk : nullptr;
+  c.ctr = d->ctr ? d->ctr + 16 * k : nullptr;
+  return c;
+}
+
+// One velocity evaluation of a chain (den_step), with the Euler update x += dt v unless it has a velocity output.
+struct DenStep {
+  float* x;                     // input state
+  const float* mods;            // the evaluation's modulation rows (row block 0 of the chain's when `ctr` picks the block)
+  int mod_div;                  // state rows per modulation row
+  float dt;
+  hipStream_t st;
+  float* vout = nullptr;        // velocity output: no state update
+  int* ctr = nullptr;           // device step counter: the rows are read (*ctr) row blocks in, and the step advances it
+  const float* xsrc = nullptr;  // fused Euler step: the state the previous step's update starts from (den_step_impl)
+};
 
 static bool stream_capturing(hipStream_t st);
 
@@ -2051,24 +2111,7 @@ FLAMED_API int flamed_den_destroy(flamed_den_t h) {
   {
     std::lock_guard<std::recursive_mutex> lk(d->mu);
     DeviceGuard dg(d->device);
-    retire_graph(d->gexec);
-    for (auto& g : d->gexec_c) retire_graph(g);
-    if (d->cap_stream) (void)hipStreamDestroy(d->cap_stream);
-    for (auto& a : d->cap_aux)
-      if (a) (void)hipStreamDestroy(a);
-    for (auto& r : d->run_aux)
-      for (auto& a : r)
-        if (a) (void)hipStreamDestroy(a);
-    for (int i = 0; i < d->n_parked; ++i) (void)hipStreamDestroy(d->parked[i]);
-    if (d->qprobe) (void)hipFree(d->qprobe);
-    for (auto& e : d->cap_ev)
-      if (e) (void)hipEventDestroy(e);
-    if (d->ctr) (void)hipFree(d->ctr);
-    if (d->scnt) (void)hipFree(d->scnt);
-    if (d->gcnt) (void)hipFree(d->gcnt);
-    d->dlens.release();
-    persist_release(d);
-    if (d->dev) (void)hipFree(d->dev);
+    den_release_device(d);
   }
   delete d;
   return kOk;
@@ -2109,27 +2152,7 @@ FLAMED_API int flamed_den_load(flamed_den_t h, const float* const* w, int n, hip
   std::lock_guard<std::recursive_mutex> lk(d->mu);
   if (d->device >= 0 && d->device != wdev) {  // re-load onto another device: drop the old device's state
     DeviceGuard og(d->device);
-    retire_graph(d->gexec);
-    for (auto& g : d->gexec_c) retire_graph(g);
-    if (d->cap_stream) { (void)hipStreamDestroy(d->cap_stream); d->cap_stream = nullptr; }
-    for (auto& a : d->cap_aux)
-      if (a) { (void)hipStreamDestroy(a); a = nullptr; }
-    for (auto& r : d->run_aux)
-      for (auto& a : r)
-        if (a) { (void)hipStreamDestroy(a); a = nullptr; }
-    for (int i = 0; i < d->n_parked; ++i) (void)hipStreamDestroy(d->parked[i]);
-    d->n_parked = 0;
-    if (d->qprobe) { (void)hipFree(d->qprobe); d->qprobe = nullptr; }
-    for (auto& e : d->cap_ev)
-      if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    if (d->ctr) { (void)hipFree(d->ctr); d->ctr = nullptr; }
-    if (d->scnt) { (void)hipFree(d->scnt); d->scnt = nullptr; }
-    if (d->gcnt) { (void)hipFree(d->gcnt); d->gcnt = nullptr; }
-    d->dlens.release();
-    d->g_lens = nullptr;
-    persist_release(d);
-    if (d->dev) { (void)hipFree(d->dev); d->dev = nullptr; }
-    d->pdev_ok = -1;
+    den_release_device(d);
   }
   d->device = wdev;
   FL_ON_DEVICE(wdev);
@@ -2269,8 +2292,7 @@ FLAMED_API int flamed_den_load(flamed_den_t h, const float* const* w, int n, hip
     const int crc = den_chain_streams(d, std::max(2, std::min(tn().split_batch, (int)Den::kMaxSplit)), st);
     if (crc) return crc;
   }
-  retire_graph(d->gexec);
-  for (auto& g : d->gexec_c) retire_graph(g);
+  d->graphs.retire();
   return kOk;
 }
 
@@ -2418,21 +2440,24 @@ static int big_euler_proj_in(Den* d, float* xt, const DenWs& w, XT* X, int* ctr,
 // across rows -- the depthwise conv + GroupNorm sub-block, the conv_out tap combine and the state update -- end every
 // utterance at its own length, everything else is row-local and computes the padding rows for nobody.
 template <typename DT, typename XT, class End>
-static int den_step_impl(Den* d, float* xt, const float* mods, int mod_div, int B, int T, float dt, float* vout,
-                         const DenWs& w, int* ctr, hipStream_t st, const float* xsrc, int Bs, int chain, int nchains, End end) {
-  const int M = B * T, H = d->H, C = d->C, MS = d->MS;
+static int den_step_impl(Den* d, const DenChain& c, const DenStep& a, End end) {
+  const int B = c.Bk, T = c.T, M = B * T, H = d->H, C = d->C, MS = d->MS;
+  const DenWs& w = c.w;
+  float* const xt = a.x; float* const vout = a.vout; int* const ctr = a.ctr;
+  const float* const mods = a.mods; const float* const xsrc = a.xsrc;
+  const int mod_div = a.mod_div; const float dt = a.dt; const hipStream_t st = a.st;
   const Tune& tu = tn();
   // a step's modulation rows are Bs apart (Bs = B, or the whole batch when this is one of its sub-batches)
-  const StepOff so{tu.noctr ? nullptr : ctr, (long long)Bs * MS};
+  const StepOff so{tu.noctr ? nullptr : ctr, (long long)c.Bs * MS};
   SplitCtx sctx;
   // sub-batch chains (den_split) each own 1/nchains of the split-K and GroupNorm counters
-  const int scn = Den::kSplitCounters / nchains, gcn = Den::kGnCounters / nchains;
-  sctx.slab = w.SL; sctx.slab_floats = w.SLn; sctx.cnt = d->scnt ? d->scnt + (size_t)chain * scn : nullptr;
+  const int scn = Den::kSplitCounters / c.nchains, gcn = Den::kGnCounters / c.nchains;
+  sctx.slab = w.SL; sctx.slab_floats = w.SLn; sctx.cnt = d->scnt ? d->scnt + (size_t)c.chain * scn : nullptr;
   sctx.cnt_n = scn;
   sctx.target = tu.split_target; sctx.max_split = tu.split_max;
   SplitScope split_scope(w.SLn ? &sctx : nullptr);
   // GroupNorm finalize fused into the depthwise-conv kernel when the counters cover B x H/64
-  int* gcnt = (d->gcnt && (size_t)B * (H / 16) <= (size_t)gcn) ? d->gcnt + (size_t)chain * gcn : nullptr;  // >= 16-channel groups
+  int* gcnt = (d->gcnt && (size_t)B * (H / 16) <= (size_t)gcn) ? d->gcnt + (size_t)c.chain * gcn : nullptr;  // >= 16-channel groups
   const GemmCfg cfg = (tu.bn32 && M < kTinyRows) ? kCfgTiny
                       : (std::is_same<DT, bf16>::value && tu.big && M >= tu.big_min_rows) ? kCfgLarge : pick_cfg(M);
   const bool big = std::is_same<DT, bf16>::value && cfg == kCfgLarge && tu.big;
@@ -2468,10 +2493,14 @@ static int den_step_impl(Den* d, float* xt, const float* mods, int mod_div, int 
   bf16* const As = reinterpret_cast<bf16*>(w.D);
   int rc;
 #define TRY(x) do { if ((rc = (x)) != kOk) return rc; } while (0)
-  int n_launched = 0;  // kernel-class launches so far (diagnostic stop_after)
+  int n_launched = 0;    // kernel-class launches so far (diagnostic stop_after)
+  bool stopped = false;  // stop_after ended the step (inside conv_sub: the step returns behind it)
 #define K_(cls, x)                                                  \
   do {                                                              \
-    if (tu.stop_after >= 0 && n_launched >= tu.stop_after) return kOk; \
+    if (tu.stop_after >= 0 && n_launched >= tu.stop_after) {        \
+      stopped = true;                                               \
+      return kOk;                                                   \
+    }                                                               \
     ++n_launched;                                                   \
     if (tu.stamp_class >= 0) stamp_select(cls, st);                 \
     TRY(x);                                                         \
@@ -2491,49 +2520,62 @@ static int den_step_impl(Den* d, float* xt, const float* mods, int mod_div, int 
   } else {
     K_(0, (den_gemm<DT>(cfg, false, LoadF32<DT>{xt, C}, (const DT*)d->win, C, EpiBiasStatsT<false, XT>{d->bin, X, H, w.S0, NT}, M, H, C, st)));
   }
+  // The conv sub-block -- depthwise conv + GroupNorm, conv_2, conv_3 (classes 1 to 4) -- of a block (aff: its input
+  // LayerNorm has an affine, and the fold's x * alpha rows take the block's mlp LayerNorm weight) or of the final layer;
+  // md: the sub-block's modulation vectors [shift, scale, gate, ., next scale].
+  auto conv_sub = [&](auto aff, const DenBlockW& Bw, const float* md) -> int {
+    constexpr bool AFF = decltype(aff)::value;
+    const float *const lnw = AFF ? Bw.lnw : nullptr, *const lnb = AFF ? Bw.lnb : nullptr;
+    const ModRef mc{md, md + H, MS, mod_div, so};
+    if (dwgn) {  // large M: conv + GroupNorm in one kernel, conv_2 on the normalised bf16 rows
+      K_(1, (launch_dwgn<AFF, XT, End>(X, H, w.S0, NT, BN, mc, lnw, lnb, Bw.dww, Bw.dwb, Bw.gnw, Bw.gnb, w.A16, B, T, st, end)));
+      K_(3, (den_gemm<DT>(cfg, false, LoadPlain<DT>{(const DT*)w.A16, H}, (const DT*)Bw.w2, H, EpiBiasAct<DT, 1>{Bw.b2, U, H}, M, H, H, st)));
+    } else if (dwgn_s) {
+      K_(1, (launch_dwgn_small<AFF, End>((const float*)w.X, H, w.S0, NT, BN, mc, lnw, lnb, Bw.dww, Bw.dwb, Bw.gnw, Bw.gnb, As, B, T, st, end)));
+      K_(3, (den_gemm<DT>(cfg, false, LoadPlain<DT>{(const DT*)As, H}, (const DT*)Bw.w2, H, EpiBiasAct<DT, 1>{Bw.b2, U, H}, M, H, H, st)));
+    } else {
+      K_(1, (launch_dwconv_stats<AFF, XT, End>(X, H, w.S0, NT, BN, mc, lnw, lnb, Bw.dww, Bw.dwb, Dx, w.GP, w.GNS, B, T, st, 1, gcnt, end)));
+      K_(2, (launch_dwconv_stats<AFF, XT, End>(X, H, w.S0, NT, BN, mc, lnw, lnb, Bw.dww, Bw.dwb, Dx, w.GP, w.GNS, B, T, st, 2, gcnt, end)));
+      if (f8) {
+        K_(3, f8_prep(LoadGN<bf16>{w.D, H, w.GNS, Bw.gnw, Bw.gnb, T, D16p}, M, A8, A8s, st));
+        K_(3, launch_gemm8p_f8(A8, A8s, H, Bw.q[0], Bw.qs[0], H, EpiBiasActF8<1>{Bw.b2, U8, U8s, H}, M, H, H, st));
+      } else {
+        K_(3, (den_gemm<DT>(cfg, true, LoadGN<DT>{w.D, H, w.GNS, Bw.gnw, Bw.gnb, T, D16p}, (const DT*)Bw.w2, H,
+                            EpiBiasAct<DT, 1>{Bw.b2, U, H}, M, H, H, st)));
+      }
+    }
+    if (f8) {
+      K_(4, launch_gemm8p_f8(U8, U8s, H, Bw.q[1], Bw.qs[1], H,
+                             EpiConvNeXtResid<AFF, XT>{Bw.b3, X, H, w.S0, NT, BN, 1e-6f, mc, md + 2 * H, lnw, lnb, w.S1, NT}, M, H, H, st));
+    } else if (fold) {  // conv_3's epilogue also writes x * alpha for the LayerNorm-folded GEMM behind it
+      K_(4, (den_gemm<DT>(cfg, false, LoadPlain<DT>{U, H}, (const DT*)Bw.w3, H,
+                          EpiConvNeXtResid<AFF, XT>{Bw.b3, X, H, w.S0, NT, BN, 1e-6f, mc, md + 2 * H, lnw, lnb, w.S1, NT,
+                                                    w.XA, AFF ? Bw.lnmw : nullptr, md + 4 * H},
+                          M, H, H, st)));
+    } else {
+      K_(4, (den_gemm<DT>(cfg, false, LoadPlain<DT>{U, H}, (const DT*)Bw.w3, H,
+                          EpiConvNeXtResid<AFF, XT>{Bw.b3, X, H, w.S0, NT, BN, 1e-6f, mc, md + 2 * H, lnw, lnb, w.S1, NT}, M, H, H, st)));
+    }
+    return kOk;
+  };
   for (int i = 0; i < d->NB; ++i) {
     const DenBlockW& Bw = d->blk[i];
     const float* md = mods + (size_t)i * 6 * H;
-    ModRef mc{md, md + H, MS, mod_div, so};
     ModRef mm{md + 3 * H, md + 4 * H, MS, mod_div, so};
+    TRY(conv_sub(std::true_type(), Bw, md));
+    if (stopped) return kOk;
     if (f8) {
-      K_(1, (launch_dwconv_stats<true, XT, End>(X, H, w.S0, NT, BN, mc, Bw.lnw, Bw.lnb, Bw.dww, Bw.dwb, Dx, w.GP, w.GNS, B, T, st, 1, gcnt, end)));
-      K_(2, (launch_dwconv_stats<true, XT, End>(X, H, w.S0, NT, BN, mc, Bw.lnw, Bw.lnb, Bw.dww, Bw.dwb, Dx, w.GP, w.GNS, B, T, st, 2, gcnt, end)));
-      K_(3, f8_prep(LoadGN<bf16>{w.D, H, w.GNS, Bw.gnw, Bw.gnb, T, D16p}, M, A8, A8s, st));
-      K_(3, launch_gemm8p_f8(A8, A8s, H, Bw.q[0], Bw.qs[0], H, EpiBiasActF8<1>{Bw.b2, U8, U8s, H}, M, H, H, st));
-      K_(4, launch_gemm8p_f8(U8, U8s, H, Bw.q[1], Bw.qs[1], H,
-                             EpiConvNeXtResid<true, XT>{Bw.b3, X, H, w.S0, NT, BN, 1e-6f, mc, md + 2 * H, Bw.lnw, Bw.lnb, w.S1, NT},
-                             M, H, H, st));
       K_(5, f8_prep(LoadLNMod<bf16, true>{w.X, H, w.S1, NT, BN, 1e-6f, mm, Bw.lnmw, Bw.lnmb, H, X16p}, M, A8, A8s, st));
       K_(5, launch_gemm8p_f8(A8, A8s, H, Bw.q[2], Bw.qs[2], H, EpiBiasActF8<2>{Bw.mb0, U8, U8s, H}, M, H, H, st));
       K_(6, launch_gemm8p_f8(U8, U8s, H, Bw.q[3], Bw.qs[3], H,
                              EpiGatedResidT<XT>{Bw.mb2, X, H, md + 5 * H, MS, mod_div, w.S0, NT, so}, M, H, H, st));
       continue;
     }
-    if (dwgn) {  // large M: conv + GroupNorm in one kernel, conv_2 on the normalised bf16 rows
-      K_(1, (launch_dwgn<true, XT, End>(X, H, w.S0, NT, BN, mc, Bw.lnw, Bw.lnb, Bw.dww, Bw.dwb, Bw.gnw, Bw.gnb, w.A16, B, T, st, end)));
-      K_(3, (den_gemm<DT>(cfg, false, LoadPlain<DT>{(const DT*)w.A16, H}, (const DT*)Bw.w2, H, EpiBiasAct<DT, 1>{Bw.b2, U, H}, M, H, H, st)));
-    } else if (dwgn_s) {
-      K_(1, (launch_dwgn_small<true, End>((const float*)w.X, H, w.S0, NT, BN, mc, Bw.lnw, Bw.lnb, Bw.dww, Bw.dwb, Bw.gnw, Bw.gnb, As, B, T, st, end)));
-      K_(3, (den_gemm<DT>(cfg, false, LoadPlain<DT>{(const DT*)As, H}, (const DT*)Bw.w2, H, EpiBiasAct<DT, 1>{Bw.b2, U, H}, M, H, H, st)));
-    } else {
-      K_(1, (launch_dwconv_stats<true, XT, End>(X, H, w.S0, NT, BN, mc, Bw.lnw, Bw.lnb, Bw.dww, Bw.dwb, Dx, w.GP, w.GNS, B, T, st, 1, gcnt, end)));
-      K_(2, (launch_dwconv_stats<true, XT, End>(X, H, w.S0, NT, BN, mc, Bw.lnw, Bw.lnb, Bw.dww, Bw.dwb, Dx, w.GP, w.GNS, B, T, st, 2, gcnt, end)));
-      K_(3, (den_gemm<DT>(cfg, true, LoadGN<DT>{w.D, H, w.GNS, Bw.gnw, Bw.gnb, T, D16p}, (const DT*)Bw.w2, H,
-                                          EpiBiasAct<DT, 1>{Bw.b2, U, H}, M, H, H, st)));
-    }
     if (fold) {  // mlp.0 on x * alpha (written by conv_3's epilogue) with the LayerNorm in its epilogue
-      K_(4, (den_gemm<DT>(cfg, false, LoadPlain<DT>{U, H}, (const DT*)Bw.w3, H,
-                                          EpiConvNeXtResid<true, XT>{Bw.b3, X, H, w.S0, NT, BN, 1e-6f, mc, md + 2 * H, Bw.lnw, Bw.lnb, w.S1, NT,
-                                                                 w.XA, Bw.lnmw, md + 4 * H},
-                                          M, H, H, st)));
       K_(5, (den_gemm<DT>(cfg, false, LoadPlain<DT>{(const DT*)w.XA, H}, (const DT*)Bw.m0, H,
                                           EpiLNFold<DT, 2>{U, H, w.S1, NT, BN, 1e-6f, mods + d->MS0 + (size_t)i * 2 * H, H, MS, mod_div, so},
                                           M, H, H, st)));
     } else {
-      K_(4, (den_gemm<DT>(cfg, false, LoadPlain<DT>{U, H}, (const DT*)Bw.w3, H,
-                                          EpiConvNeXtResid<true, XT>{Bw.b3, X, H, w.S0, NT, BN, 1e-6f, mc, md + 2 * H, Bw.lnw, Bw.lnb, w.S1, NT},
-                                          M, H, H, st)));
       K_(5, (den_gemm<DT>(cfg, true, LoadLNMod<DT, true>{w.X, H, w.S1, NT, BN, 1e-6f, mm, Bw.lnmw, Bw.lnmb, H, X16p}, (const DT*)Bw.m0, H,
                                           EpiBiasAct<DT, 2>{Bw.mb0, U, H}, M, H, H, st)));
     }
@@ -2541,43 +2583,14 @@ static int den_step_impl(Den* d, float* xt, const float* mods, int mod_div, int 
                                         EpiGatedResidT<XT>{Bw.mb2, X, H, md + 5 * H, MS, mod_div, w.S0, NT, so}, M, H, H, st)));
   }
   const float* mf = mods + (size_t)d->NB * 6 * H;
-  ModRef mc{mf, mf + H, MS, mod_div, so};
   ModRef mo{mf + 3 * H, mf + 4 * H, MS, mod_div, so};
-  const DenBlockW& F = d->fin;
-  if (f8) {
-    K_(1, (launch_dwconv_stats<false, XT, End>(X, H, w.S0, NT, BN, mc, nullptr, nullptr, F.dww, F.dwb, Dx, w.GP, w.GNS, B, T, st, 1, gcnt, end)));
-    K_(2, (launch_dwconv_stats<false, XT, End>(X, H, w.S0, NT, BN, mc, nullptr, nullptr, F.dww, F.dwb, Dx, w.GP, w.GNS, B, T, st, 2, gcnt, end)));
-    K_(3, f8_prep(LoadGN<bf16>{w.D, H, w.GNS, F.gnw, F.gnb, T, D16p}, M, A8, A8s, st));
-    K_(3, launch_gemm8p_f8(A8, A8s, H, F.q[0], F.qs[0], H, EpiBiasActF8<1>{F.b2, U8, U8s, H}, M, H, H, st));
-  } else if (dwgn) {
-    K_(1, (launch_dwgn<false, XT, End>(X, H, w.S0, NT, BN, mc, nullptr, nullptr, F.dww, F.dwb, F.gnw, F.gnb, w.A16, B, T, st, end)));
-    K_(3, (den_gemm<DT>(cfg, false, LoadPlain<DT>{(const DT*)w.A16, H}, (const DT*)F.w2, H, EpiBiasAct<DT, 1>{F.b2, U, H}, M, H, H, st)));
-  } else if (dwgn_s) {
-    K_(1, (launch_dwgn_small<false, End>((const float*)w.X, H, w.S0, NT, BN, mc, nullptr, nullptr, F.dww, F.dwb, F.gnw, F.gnb, As, B, T, st, end)));
-    K_(3, (den_gemm<DT>(cfg, false, LoadPlain<DT>{(const DT*)As, H}, (const DT*)F.w2, H, EpiBiasAct<DT, 1>{F.b2, U, H}, M, H, H, st)));
-  } else {
-    K_(1, (launch_dwconv_stats<false, XT, End>(X, H, w.S0, NT, BN, mc, nullptr, nullptr, F.dww, F.dwb, Dx, w.GP, w.GNS, B, T, st, 1, gcnt, end)));
-    K_(2, (launch_dwconv_stats<false, XT, End>(X, H, w.S0, NT, BN, mc, nullptr, nullptr, F.dww, F.dwb, Dx, w.GP, w.GNS, B, T, st, 2, gcnt, end)));
-    K_(3, (den_gemm<DT>(cfg, true, LoadGN<DT>{w.D, H, w.GNS, F.gnw, F.gnb, T, D16p}, (const DT*)F.w2, H, EpiBiasAct<DT, 1>{F.b2, U, H}, M, H, H, st)));
-  }
-  if (f8) {
-    K_(4, launch_gemm8p_f8(U8, U8s, H, F.q[1], F.qs[1], H,
-                           EpiConvNeXtResid<false, XT>{F.b3, X, H, w.S0, NT, BN, 1e-6f, mc, mf + 2 * H, nullptr, nullptr, w.S1, NT},
-                           M, H, H, st));
-    K_(7, (den_gemm<DT>(cfg, true, LoadLNMod<DT, false>{w.X, H, w.S1, NT, BN, 1e-6f, mo, nullptr, nullptr, H, X16p}, (const DT*)d->wout, H,
-                                        EpiBiasAct<float, 0>{nullptr, w.Y, 3 * C}, M, 3 * C, H, st)));
-  } else if (fold) {
-    K_(4, (den_gemm<DT>(cfg, false, LoadPlain<DT>{U, H}, (const DT*)F.w3, H,
-                                        EpiConvNeXtResid<false, XT>{F.b3, X, H, w.S0, NT, BN, 1e-6f, mc, mf + 2 * H, nullptr, nullptr, w.S1, NT,
-                                                                w.XA, nullptr, mf + 4 * H},
-                                        M, H, H, st)));
+  TRY(conv_sub(std::false_type(), d->fin, mf));
+  if (stopped) return kOk;
+  if (fold) {
     K_(7, (den_gemm<DT>(cfg, false, LoadPlain<DT>{(const DT*)w.XA, H}, (const DT*)d->wout, H,
                                         EpiLNFold<float, 0>{w.Y, 3 * C, w.S1, NT, BN, 1e-6f, mods + d->MS0 + (size_t)d->NB * 2 * H, 3 * C, MS, mod_div, so},
                                         M, 3 * C, H, st)));
   } else {
-    K_(4, (den_gemm<DT>(cfg, false, LoadPlain<DT>{U, H}, (const DT*)F.w3, H,
-                                        EpiConvNeXtResid<false, XT>{F.b3, X, H, w.S0, NT, BN, 1e-6f, mc, mf + 2 * H, nullptr, nullptr, w.S1, NT},
-                                        M, H, H, st)));
     K_(7, (den_gemm<DT>(cfg, true, LoadLNMod<DT, false>{w.X, H, w.S1, NT, BN, 1e-6f, mo, nullptr, nullptr, H, X16p}, (const DT*)d->wout, H,
                                         EpiBiasAct<float, 0>{nullptr, w.Y, 3 * C}, M, 3 * C, H, st)));
   }
@@ -2597,26 +2610,19 @@ static int den_step_impl(Den* d, float* xt, const float* mods, int mod_div, int 
   return kOk;
 }
 
-template <class End>
-static int den_step_end(Den* d, float* xt, const float* mods, int mod_div, int B, int T, float dt, float* vout, void* ws,
-                        hipStream_t st, int* ctr, const float* xsrc, int Bs, int chain, int nchains, End end) {
-  if (Bs <= 0) Bs = B;
-  DenWs w;
-  den_ws_layout(d, B, T, ws, &w);
-  if (d->dt == FLAMED_BF16) {
-    if (den_x16(d, B, T))
-      return den_step_impl<bf16, bf16>(d, xt, mods, mod_div, B, T, dt, vout, w, ctr, st, xsrc, Bs, chain, nchains, end);
-    return den_step_impl<bf16, float>(d, xt, mods, mod_div, B, T, dt, vout, w, ctr, st, xsrc, Bs, chain, nchains, end);
-  }
-  return den_step_impl<float, float>(d, xt, mods, mod_div, B, T, dt, vout, w, ctr, st, xsrc, Bs, chain, nchains, end);
+// f(end) with the sequence-end policy of the denoiser's kernels: every utterance ended at its own length (lens: B device
+// ints of an exact-lengths solve), or dense (null).
+template <class F>
+static int with_seq_end(const int* lens, F&& f) {
+  return lens ? f(SeqEnd<true>::make(lens, 1)) : f(SeqEnd<false>());
 }
-// lens (B device ints, or null = dense): the utterances' own lengths of an exact-lengths solve
-static int den_step(Den* d, float* xt, const float* mods, int mod_div, int B, int T, float dt, float* vout, void* ws,
-                    hipStream_t st, int* ctr = nullptr, const float* xsrc = nullptr, int Bs = 0, int chain = 0,
-                    int nchains = 1, const int* lens = nullptr) {
-  if (lens)
-    return den_step_end(d, xt, mods, mod_div, B, T, dt, vout, ws, st, ctr, xsrc, Bs, chain, nchains, SeqEnd<true>::make(lens, 1));
-  return den_step_end(d, xt, mods, mod_div, B, T, dt, vout, ws, st, ctr, xsrc, Bs, chain, nchains, SeqEnd<false>());
+
+static int den_step(Den* d, const DenChain& c, const DenStep& a) {
+  return with_seq_end(c.lens, [&](auto end) -> int {
+    if (d->dt == FLAMED_BF16 && den_x16(d, c.Bk, c.T)) return den_step_impl<bf16, bf16>(d, c, a, end);
+    if (d->dt == FLAMED_BF16) return den_step_impl<bf16, float>(d, c, a, end);
+    return den_step_impl<float, float>(d, c, a, end);
+  });
 }
 
 // The fused Euler step (LoadEulerIn) runs where proj_in takes the small-M register loop with one
@@ -2636,9 +2642,6 @@ static bool den_fused_big(const Den* d, int B, int T) {
          !(tu.bn32 && (size_t)B * T < (size_t)kTinyRows);
 }
 
-// Steps per captured graph: the largest divisor of nfe that is <= tn().graph_steps (default 16; the
-// graph is replayed nfe/G times per solve, so a new (B, T) costs one G-step capture instead of an
-// nfe-step one).
 // ------------------------------ persistent B = 1 solve (persist.hpp) ------------------------------
 
 // Scratch of the persistent solve, sized for T <= pk::kMaxT: the counter block (reset by every launch's own
@@ -2846,33 +2849,109 @@ static int persist_solve(Den* d, float* xt, const float* mods, int nfe, int B, i
 static int launch_combine(const float* Y, const float* bias, float* xt, int M, int T, int C, float dt, const float* src,
                           const int* lens, hipStream_t st) {
   const size_t n = (size_t)M * C;
-  if (lens)
-    hipLaunchKernelGGL(conv3_combine_kernel<SeqEnd<true>>, dim3((n + 255) / 256), dim3(256), 0, st, Y, bias, xt, (float*)nullptr, M, T,
-                       C, dt, (int*)nullptr, src, SeqEnd<true>::make(lens, 1));
-  else
-    hipLaunchKernelGGL(conv3_combine_kernel<SeqEnd<false>>, dim3((n + 255) / 256), dim3(256), 0, st, Y, bias, xt, (float*)nullptr, M, T,
-                       C, dt, (int*)nullptr, src, SeqEnd<false>());
-  FL_LAUNCH_CHECK();
-  return kOk;
+  return with_seq_end(lens, [&](auto end) -> int {
+    hipLaunchKernelGGL(conv3_combine_kernel<decltype(end)>, dim3((n + 255) / 256), dim3(256), 0, st, Y, bias, xt, (float*)nullptr, M,
+                       T, C, dt, (int*)nullptr, src, end);
+    FL_LAUNCH_CHECK();
+    return kOk;
+  });
 }
 static int launch_rk2_update(const float* xb, const float* y, const float* v, float* xo, int M, int T, int C, float c1, float g,
                              const int* lens, hipStream_t st) {
   const size_t n = (size_t)M * C;
-  if (lens)
-    hipLaunchKernelGGL(rk2_update_kernel<SeqEnd<true>>, dim3((n + 255) / 256), dim3(256), 0, st, xb, y, v, xo, n, c1, g, T, C,
-                       SeqEnd<true>::make(lens, 1));
-  else
-    hipLaunchKernelGGL(rk2_update_kernel<SeqEnd<false>>, dim3((n + 255) / 256), dim3(256), 0, st, xb, y, v, xo, n, c1, g, T, C,
-                       SeqEnd<false>());
-  FL_LAUNCH_CHECK();
-  return kOk;
+  return with_seq_end(lens, [&](auto end) -> int {
+    hipLaunchKernelGGL(rk2_update_kernel<decltype(end)>, dim3((n + 255) / 256), dim3(256), 0, st, xb, y, v, xo, n, c1, g, T, C, end);
+    FL_LAUNCH_CHECK();
+    return kOk;
+  });
 }
 
+// Steps per captured graph: the largest divisor of nfe that is <= tn().graph_steps (default 16; the
+// graph is replayed nfe/G times per solve, so a new (B, T) costs one G-step capture instead of an
+// nfe-step one).
 static int graph_chunk(int nfe, int per_step = 1) {
   const int gs = tn().graph_steps / per_step;  // (per_step launches-worth of Euler steps per solver step)
   for (int g = gs < nfe ? gs : nfe; g > 1; --g)
     if (nfe % g == 0) return g;
   return 1;
+}
+
+// The step structure of one solve on the launch path, decided once (den_solve_range; the timing graph of
+// flamed_den_time_kernels_graph):
+//   kEuler     one den_step per step, its own combine + Euler update at its end (26 launches);
+//   kPingPong  fused Euler steps at small M (den_fused_ok; 25 launches: the combine rides in the next proj_in): the state
+//              ping-pongs between x (even steps) and the workspace's XP (odd steps), so G must be even;
+//   kInPlace   fused Euler steps at large M (den_fused_big), in place, per chain;
+//   kRk2       a two-stage solver: evaluation e is v(x) into XV and y = x + (a dt) v into XP (e even), or v(y) and the
+//              step x += c1 (y - x) + (c2 dt) v in place (e odd); neither fusion, every evaluation writes its velocity.
+struct SolvePlan {
+  enum Mode { kEuler, kPingPong, kInPlace, kRk2 } mode;
+  int S, Bk;        // sub-batch chains (den_split) and the utterances of each
+  int G;            // steps per captured graph; 0: eager launches, which take no fusion
+  bool branches;    // tune split_graph 1: the chains as parallel branches of one graph
+  float dt;         // Euler step
+  const Rk2* rk;    // kRk2: the solver's coefficients
+  bool fused() const { return mode == kPingPong || mode == kInPlace; }
+};
+static SolvePlan solve_plan(const Den* d, int B, int T, int S, int G, float dt, const Rk2* rk) {
+  SolvePlan p;
+  p.S = S; p.Bk = B / S; p.G = G; p.dt = dt; p.rk = rk;
+  p.branches = S > 1 && tn().split_graph == 1;
+  p.mode = rk ? SolvePlan::kRk2
+           : G == 0 ? SolvePlan::kEuler
+           : S == 1 && den_fused_ok(d, B, T) && G % 2 == 0 ? SolvePlan::kPingPong
+           : den_fused_big(d, p.Bk, T) ? SolvePlan::kInPlace : SolvePlan::kEuler;
+  return p;
+}
+
+// Step (kRk2: evaluation) s of chain c, enqueued on cs.  A captured step reads its modulation rows where the chain's
+// device counter says (row_off 0, ctr = c.ctr); an eager one reads row block s (row_off = s row blocks, no counter).
+static int plan_step(Den* d, const SolvePlan& p, const DenChain& c, int s, size_t row_off, int* ctr, hipStream_t cs) {
+  DenStep a{c.x, c.mods + row_off, c.T, p.dt, cs, nullptr, ctr};
+  const bool odd = s & 1;
+  switch (p.mode) {
+    case SolvePlan::kEuler: break;
+    case SolvePlan::kPingPong: a.x = odd ? c.w.XP : c.x; a.xsrc = odd ? c.x : c.w.XP; break;
+    case SolvePlan::kInPlace: a.xsrc = c.x; break;
+    case SolvePlan::kRk2: {
+      a.x = odd ? c.w.XP : c.x; a.dt = 0.f; a.vout = c.w.XV;
+      const int rc = den_step(d, c, a);
+      if (rc) return rc;
+      return launch_rk2_update(c.x, odd ? c.w.XP : (const float*)nullptr, c.w.XV, odd ? c.x : c.w.XP, c.Bk * c.T, c.T, d->C,
+                               odd ? p.rk->c1 : 0.f, odd ? p.rk->c2dt : p.rk->adt, c.lens, cs);
+    }
+  }
+  return den_step(d, c, a);
+}
+// A fused solve's state ahead of its first step: a Y whose combine is exactly 0 (and x in XP for the ping-pong).
+static int plan_init_state(Den* d, const SolvePlan& p, const DenChain& c, hipStream_t st) {
+  const size_t n = (size_t)c.Bk * c.T * d->C;
+  hipLaunchKernelGGL(euler_init_kernel, dim3((n + 255) / 256), dim3(256), 0, st, c.x, d->bout,
+                     p.mode == SolvePlan::kPingPong ? c.w.XP : (float*)nullptr, c.w.Y, c.Bk * c.T, d->C);
+  FL_LAUNCH_CHECK();
+  return kOk;
+}
+// Before the first replay of a solve: the step counters of every chain (16 ints apart) at 0, or for fused steps the
+// initial state and counter -1 (each step's proj_in advances it before the step's first modulation read).
+static int plan_begin(Den* d, const SolvePlan& p, const DenChain* ch, hipStream_t st) {
+  if (!p.fused()) FL_HIP(hipMemsetAsync(d->ctr, 0, 256, st));
+  for (int k = 0; p.fused() && k < p.S; ++k) {
+    const int rc = plan_init_state(d, p, ch[k], st);
+    if (rc) return rc;
+    FL_HIP(hipMemsetAsync(ch[k].ctr, 0xff, sizeof(int), st));
+  }
+  return kOk;
+}
+// After the last replay: the last fused step's combine + Euler update of every chain, x_nfe = x_{nfe-1} + dt v (the
+// ping-pong's x_{nfe-1} is in XP: nfe is even).
+static int plan_end(Den* d, const SolvePlan& p, const DenChain* ch, hipStream_t st) {
+  for (int k = 0; p.fused() && k < p.S; ++k) {
+    const DenChain& c = ch[k];
+    const int rc = launch_combine(c.w.Y, d->bout, c.x, c.Bk * c.T, c.T, d->C, p.dt, p.mode == SolvePlan::kPingPong ? c.w.XP : nullptr,
+                                  c.lens, st);
+    if (rc) return rc;
+  }
+  return kOk;
 }
 
 }  // namespace fl
@@ -2890,7 +2969,8 @@ FLAMED_API int flamed_den_velocity(flamed_den_t h, const float* x, const float* 
     set_error("flamed_den_velocity: workspace too small (%zu < %zu)", ws_bytes, den_ws_bytes(d, B, T));
     return kNoWorkspace;
   }
-  return den_step(d, const_cast<float*>(x), mods, mod_div, B, T, 0.f, v_out, ws, st);
+  float* const xin = const_cast<float*>(x);
+  return den_step(d, den_chain(d, xin, mods, ws, B, T, 1, nullptr, 0), DenStep{xin, mods, mod_div, 0.f, st, v_out});
 }
 
 FLAMED_API int flamed_den_step(flamed_den_t h, float* xt, const float* mods, int mod_div, int B, int T, float dt,
@@ -2904,7 +2984,7 @@ FLAMED_API int flamed_den_step(flamed_den_t h, float* xt, const float* mods, int
     set_error("flamed_den_step: workspace too small");
     return kNoWorkspace;
   }
-  return den_step(d, xt, mods, mod_div, B, T, dt, nullptr, ws, st);
+  return den_step(d, den_chain(d, xt, mods, ws, B, T, 1, nullptr, 0), DenStep{xt, mods, mod_div, dt, st});
 }
 
 FLAMED_API int flamed_den_solve_chunk(flamed_den_t h, int nfe) {
@@ -3100,9 +3180,8 @@ static int den_chain_streams(Den* d, int S, hipStream_t st) {
 }
 
 // Velocity evaluations [s0, s1) of an nfe-evaluation solve.  rk null: forward Euler, one evaluation per step.  rk set
-// (flamed_den_solve_rk2; always the whole solve): two evaluations per step, x and the stage state y (the workspace's
-// XP) alternating as the evaluation's input, each evaluation a den_step with a velocity output (XV) followed by
-// rk2_update_kernel; modulation row block k belongs to evaluation k on every path.
+// (flamed_den_solve_rk2; always the whole solve): two evaluations per step (SolvePlan::kRk2); modulation row block k
+// belongs to evaluation k on every path.
 // mod_B > 0 (the exact-lengths fallback, plain launches only): xt is a sub-batch of B utterances whose modulation rows
 // lie in the table of a batch of mod_B, so row block k starts k * mod_B rows in.
 // dlens (B device ints, the handle's DevLens, written in stream order ahead of this call; null = dense): the ragged batch
@@ -3126,34 +3205,15 @@ static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe
   const float dt = (float)(1.0 / (double)nfe);
   FL_REQUIRE(mod_B == 0 || (mod_B >= B && !(use_graph & 1)), "flamed_den_solve: a sub-batch solve runs plain launches");
   const size_t step_stride = (size_t)(mod_B ? mod_B : B) * d->MS;
-  const int S = den_split(d, B, T), Bk = B / S;
-  const size_t wsk = S > 1 ? den_split_ws(d, B, T, S) : 0;
-  auto sub = [&](int k, float*& xk, const float*& mk, void*& wk) {  // chain k's state, table rows, workspace
-    xk = xt + (size_t)k * Bk * T * d->C;
-    mk = mods + (size_t)k * Bk * d->MS;
-    wk = static_cast<char*>(ws) + k * wsk;
-  };
-  auto lens_of = [&](int k) -> const int* { return dlens ? dlens + (size_t)k * Bk : nullptr; };  // chain k's lengths
-  // evaluation e of a two-stage solve on chain k: v(x) into XV, then y = x + (a dt) v into XP (e even), or v(y)
-  // and the step x += c1 (y - x) + (c2 dt) v in place (e odd)
-  auto rk_eval = [&](int e, int k, const float* mrow, hipStream_t cs, int* ctr) -> int {
-    float* xk; const float* mk; void* wk;
-    sub(k, xk, mk, wk);
-    DenWs wc;
-    den_ws_layout(d, Bk, T, wk, &wc);
-    const bool first = !(e & 1);
-    const int rc = den_step(d, first ? xk : wc.XP, mrow ? mrow : mk, T, Bk, T, 0.f, wc.XV, wk, cs, ctr, nullptr, B, k, S, lens_of(k));
-    if (rc) return rc;
-    return launch_rk2_update(xk, first ? (const float*)nullptr : wc.XP, wc.XV, first ? wc.XP : xk, Bk * T, T, d->C,
-                             first ? 0.f : rk->c1, first ? rk->adt : rk->c2dt, lens_of(k), cs);
-  };
+  const int S = den_split(d, B, T);
+  DenChain ch[Den::kMaxSplit];  // (laid out after the path decision: a persistent launch has no chains)
+  auto chains = [&] { for (int k = 0; k < S; ++k) ch[k] = den_chain(d, xt, mods, ws, B, T, S, dlens, k); };
   if (!(use_graph & 1)) {
+    const SolvePlan p = solve_plan(d, B, T, S, 0, dt, rk);
+    chains();
     for (int s = s0; s < s1; ++s)
       for (int k = 0; k < S; ++k) {
-        float* xk; const float* mk; void* wk;
-        sub(k, xk, mk, wk);
-        int rc = rk ? rk_eval(s, k, mk + s * step_stride, st, nullptr)
-                    : den_step(d, xk, mk + s * step_stride, T, Bk, T, dt, nullptr, wk, st, nullptr, nullptr, B, k, S, lens_of(k));
+        const int rc = plan_step(d, p, ch[k], s, s * step_stride, nullptr, st);
         if (rc) return rc;
       }
     return kOk;
@@ -3181,21 +3241,17 @@ static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe
     d->pdev_ok = 0;
     d->ppath = 0;
   }
-  if (!d->ctr) FL_HIP(hipMalloc(&d->ctr, 256));
-  // fused Euler steps: 25 launches per step instead of 26 (the combine rides in the next proj_in); the
-  // state ping-pongs between xt (even steps) and the workspace's XP (odd steps), so G must be even
-  // (two-stage solvers take neither fusion: every evaluation writes its velocity)
-  const bool fused = !rk && S == 1 && den_fused_ok(d, B, T) && G % 2 == 0;
-  const bool fbig = !rk && !fused && den_fused_big(d, Bk, T);  // large M: in-place fused steps, per chain
-  const bool br = S > 1 && tn().split_graph == 1;
-  DenWs w;
-  den_ws_layout(d, B, T, ws, &w);
-  // the graph bakes in dt = 1/nfe (and a two-stage solver's coefficients), so nfe and the solver are part of the key
-  const bool hit = d->gexec && d->g_B == B && d->g_T == T && d->g_nfe == nfe && d->g_xt == xt && d->g_mods == mods && d->g_ws == ws &&
-                   d->g_epoch == d->tune_ver && d->g_a == (rk ? rk->a : 0.0) && d->g_lens == dlens;
-  if (!hit) {
-    retire_graph(d->gexec);
-    for (auto& g : d->gexec_c) retire_graph(g);
+  const SolvePlan p = solve_plan(d, B, T, S, G, dt, rk);
+  const bool br = p.branches;
+  chains();
+  // the graphs bake in dt = 1/nfe (and a two-stage solver's coefficients), so nfe and the solver (the bit pattern of
+  // its stage parameter, 0 for Euler) are part of the key
+  uint64_t abits = 0;
+  if (rk) memcpy(&abits, &rk->a, sizeof(abits));
+  const std::vector<const void*> key = {(const void*)(intptr_t)B, (const void*)(intptr_t)T, (const void*)(intptr_t)nfe, xt, mods, ws,
+                                        (const void*)(intptr_t)d->tune_ver, (const void*)(uintptr_t)abits, dlens};
+  if (!d->graphs.hit(key)) {
+    d->graphs.retire();
     if (!d->cap_stream) FL_HIP(hipStreamCreateWithFlags(&d->cap_stream, hipStreamNonBlocking));
     if (S > 1 && !br) {
       const int rc = den_chain_streams(d, S, st);
@@ -3203,21 +3259,19 @@ static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe
     }
     for (int k = 0; k < Den::kMaxSplit; ++k)
       if (!d->cap_ev[k]) FL_HIP(hipEventCreateWithFlags(&d->cap_ev[k], hipEventDisableTiming));
+    auto chunk = [&](int k, hipStream_t cs) -> int {  // the G counter-driven steps of chain k
+      int rc = kOk;
+      for (int s = 0; s < G && rc == kOk; ++s) rc = plan_step(d, p, ch[k], s, 0, ch[k].ctr, cs);
+      return rc;
+    };
     if (br) {  // tune split_graph 1 (round 4): one graph, the chains as parallel branches (fork / join events)
       for (int k = 1; k < S; ++k)
         if (!d->cap_aux[k]) FL_HIP(hipStreamCreateWithFlags(&d->cap_aux[k], hipStreamNonBlocking));
-      const int crc = capture_exec(d->cap_stream, &d->gexec, [&](hipStream_t cap) -> int {
+      const int crc = capture_exec(d->cap_stream, &d->graphs.exec[0], [&](hipStream_t cap) -> int {
         FL_HIP(hipEventRecord(d->cap_ev[0], cap));
         for (int k = 1; k < S; ++k) FL_HIP(hipStreamWaitEvent(d->cap_aux[k], d->cap_ev[0], 0));
         int rc = kOk;
-        for (int k = 0; k < S && rc == kOk; ++k) {
-          float* xk; const float* mk; void* wk;
-          sub(k, xk, mk, wk);
-          hipStream_t cs = k == 0 ? cap : d->cap_aux[k];
-          for (int s = 0; s < G && rc == kOk; ++s)
-            rc = rk ? rk_eval(s, k, nullptr, cs, d->ctr + 16 * k)
-                    : den_step(d, xk, mk, T, Bk, T, dt, nullptr, wk, cs, d->ctr + 16 * k, fbig ? xk : nullptr, B, k, S, lens_of(k));
-        }
+        for (int k = 0; k < S && rc == kOk; ++k) rc = chunk(k, k == 0 ? cap : d->cap_aux[k]);
         for (int k = 1; k < S && rc == kOk; ++k) {
           FL_HIP(hipEventRecord(d->cap_ev[k], d->cap_aux[k]));
           FL_HIP(hipStreamWaitEvent(cap, d->cap_ev[k], 0));
@@ -3228,46 +3282,17 @@ static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe
     }
     // one graph per chain (G steps of its sub-batch), captured one after another on cap_stream
     for (int k = 0; k < (br ? 0 : S); ++k) {
-      const int crc = capture_exec(d->cap_stream, k == 0 ? &d->gexec : &d->gexec_c[k], [&](hipStream_t cap) -> int {
-        int rc = kOk;
-        float* xk; const float* mk; void* wk;
-        sub(k, xk, mk, wk);
-        for (int s = 0; s < G && rc == kOk; ++s) {
-          if (rk) rc = rk_eval(s, k, nullptr, cap, d->ctr + 16 * k);
-          else if (fused) rc = den_step(d, s % 2 ? w.XP : xt, mods, T, B, T, dt, nullptr, ws, cap, d->ctr, s % 2 ? xt : w.XP, 0, 0, 1, dlens);
-          else rc = den_step(d, xk, mk, T, Bk, T, dt, nullptr, wk, cap, d->ctr + 16 * k, fbig ? xk : nullptr, B, k, S, lens_of(k));
-        }
-        return rc;
-      });
+      const int crc = capture_exec(d->cap_stream, &d->graphs.exec[k], [&](hipStream_t cap) -> int { return chunk(k, cap); });
       if (crc) return crc;
     }
-    d->g_B = B; d->g_T = T; d->g_nfe = nfe; d->g_epoch = d->tune_ver; d->g_xt = xt; d->g_mods = mods; d->g_ws = ws;
-    d->g_a = rk ? rk->a : 0.0;
-    d->g_lens = dlens;
+    d->graphs.key = key;
   }
-  const size_t n = (size_t)B * T * d->C;
   if (s0 == 0) {
-    if (fused) {  // counter -1: each step's proj_in advances it before the step's first modulation read
-      hipLaunchKernelGGL(euler_init_kernel, dim3((n + 255) / 256), dim3(256), 0, st, xt, d->bout, w.XP, w.Y, B * T, d->C);
-      FL_LAUNCH_CHECK();
-      FL_HIP(hipMemsetAsync(d->ctr, 0xff, sizeof(int), st));
-    } else if (fbig) {  // every chain: Y whose combine is exactly 0, counter -1 (its euler_cast advances it)
-      for (int k = 0; k < S; ++k) {
-        float* xk; const float* mk; void* wk;
-        sub(k, xk, mk, wk);
-        DenWs wc;
-        den_ws_layout(d, Bk, T, wk, &wc);
-        const size_t nk = (size_t)Bk * T * d->C;
-        hipLaunchKernelGGL(euler_init_kernel, dim3((nk + 255) / 256), dim3(256), 0, st, xk, d->bout, (float*)nullptr, wc.Y, Bk * T, d->C);
-        FL_LAUNCH_CHECK();
-        FL_HIP(hipMemsetAsync(d->ctr + 16 * k, 0xff, sizeof(int), st));
-      }
-    } else {
-      FL_HIP(hipMemsetAsync(d->ctr, 0, 256, st));  // the step counters of every chain (16 ints apart)
-    }
+    const int rc = plan_begin(d, p, ch, st);
+    if (rc) return rc;
   }
+  const int NG = br ? 1 : S;  // graphs to replay
   if ((S > 1 && !br) || tn().prio_all) {  // fork: every chain replays its graph for the whole range on its stream, then join
-    const int NG = br ? 1 : S;  // graphs to replay
     if (NG == 1) {
       const int rc = den_chain_streams(d, 1, st);  // (prio_all: the single graph on a chain stream too)
       if (rc) return rc;
@@ -3278,7 +3303,7 @@ static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe
     for (int k = 0; k < NG; ++k) {
       hipStream_t cs = (k == 0 && !own0) ? st : d->run_aux[pm][k];
       if (cs != st) FL_HIP(hipStreamWaitEvent(cs, d->cap_ev[0], 0));
-      for (int r = s0 / G; r < s1 / G; ++r) FL_HIP(hipGraphLaunch(k == 0 ? d->gexec : d->gexec_c[k], cs));
+      for (int r = s0 / G; r < s1 / G; ++r) FL_HIP(hipGraphLaunch(d->graphs.exec[k], cs));
     }
     for (int k = 0; k < NG; ++k) {
       hipStream_t cs = (k == 0 && !own0) ? st : d->run_aux[pm][k];
@@ -3287,25 +3312,10 @@ static int den_solve_range(flamed_den_t h, float* xt, const float* mods, int nfe
       FL_HIP(hipStreamWaitEvent(st, d->cap_ev[1 + k % (Den::kMaxSplit - 1)], 0));
     }
   } else {
-    for (int r = s0 / G; r < s1 / G; ++r) FL_HIP(hipGraphLaunch(d->gexec, st));
+    for (int r = s0 / G; r < s1 / G; ++r) FL_HIP(hipGraphLaunch(d->graphs.exec[0], st));
   }
-  note_graph_use(d->gexec, st);
-  for (int k = 1; k < (br ? 1 : S); ++k) note_graph_use(d->gexec_c[k], st);  // st has joined chain k's replays
-  if (fused && s1 == nfe) {  // the last step's combine + Euler update: x_nfe = XP + dt * v (nfe even: XP holds x_{nfe-1})
-    const int rc = launch_combine(w.Y, d->bout, xt, B * T, T, d->C, dt, w.XP, dlens, st);
-    if (rc) return rc;
-  }
-  if (fbig && s1 == nfe) {  // every chain's last combine + Euler update, in place
-    for (int k = 0; k < S; ++k) {
-      float* xk; const float* mk; void* wk;
-      sub(k, xk, mk, wk);
-      DenWs wc;
-      den_ws_layout(d, Bk, T, wk, &wc);
-      const int rc = launch_combine(wc.Y, d->bout, xk, Bk * T, T, d->C, dt, nullptr, lens_of(k), st);
-      if (rc) return rc;
-    }
-  }
-  return kOk;
+  for (int k = 0; k < NG; ++k) note_graph_use(d->graphs.exec[k], st);  // st has joined every chain's replays
+  return s1 == nfe ? plan_end(d, p, ch, st) : kOk;
 }
 
 FLAMED_API int flamed_den_solve_part(flamed_den_t h, float* xt, const float* mods, int nfe, int B, int T, void* ws,
@@ -3369,11 +3379,7 @@ static int den_solve_lens(flamed_den_t h, float* xt, const float* mods, const in
     bool moved = false;
     const int lrc = d->dlens.put(lens, B, st, &moved);
     if (lrc) return lrc;
-    if (moved) {
-      retire_graph(d->gexec);
-      for (auto& g : d->gexec_c) retire_graph(g);
-      d->g_lens = nullptr;
-    }
+    if (moved) d->graphs.retire();
     d->lens_path = 2;
     // (bit 2: the range solver's own persistent launch is for dense batches)
     return den_solve_range(h, xt, mods, nfe, B, T, ws, ws_bytes, (use_graph & 1) | 2, 0, nfe, rk, st, 0, d->dlens.d);
@@ -3450,26 +3456,18 @@ FLAMED_API int flamed_den_time_kernels_graph(flamed_den_t h, float* xt, const fl
   FL_HIP(hipEventCreate(&guard.e1));
   hipEvent_t e0 = guard.e0, e1 = guard.e1;
   const int saved_dup = guard.dup;  // the handle's active snapshot (this call's TuneScope)
-  // the step structure the solve graph uses: fused Euler steps (no combine launches) where it fuses
-  const bool fused = den_fused_ok(d, B, T);
-  const bool fbig = !fused && den_fused_big(d, B, T);
-  DenWs w;
-  den_ws_layout(d, B, T, ws, &w);
-  if (fused || fbig) {
-    const size_t n = (size_t)B * T * d->C;
-    hipLaunchKernelGGL(euler_init_kernel, dim3((n + 255) / 256), dim3(256), 0, st, xt, d->bout, fused ? w.XP : (float*)nullptr,
-                       w.Y, B * T, d->C);
-    FL_LAUNCH_CHECK();
-  }
+  // the steps of the solve graph of one chain (fused Euler steps, without combine launches, where it fuses), with
+  // dt = 0 and the first modulation row block for every step
+  const SolvePlan p = solve_plan(d, B, T, 1, kSteps, 0.f, nullptr);
+  const DenChain whole = den_chain(d, xt, mods, ws, B, T, 1, nullptr, 0);
+  const int irc = p.fused() ? plan_init_state(d, p, whole, st) : kOk;
+  if (irc) return irc;
   auto timed = [&](int dup, float* ms) -> int {
     hipGraphExec_t ex;
     const int crc = capture_exec(d->cap_stream, &ex, [&](hipStream_t cap) -> int {
       d->tune.dup_class = dup;
       int rc = kOk;
-      for (int i = 0; i < kSteps && rc == kOk; ++i) {
-        if (fused) rc = den_step(d, i % 2 ? w.XP : xt, mods, T, B, T, 0.f, nullptr, ws, cap, nullptr, i % 2 ? xt : w.XP);
-        else rc = den_step(d, xt, mods, T, B, T, 0.f, nullptr, ws, cap, nullptr, fbig ? xt : nullptr);
-      }
+      for (int i = 0; i < kSteps && rc == kOk; ++i) rc = plan_step(d, p, whole, i, 0, nullptr, cap);
       d->tune.dup_class = saved_dup;
       return rc;
     });
@@ -3488,7 +3486,7 @@ FLAMED_API int flamed_den_time_kernels_graph(flamed_den_t h, float* xt, const fl
   float base = 0.f;
   int rc = timed(-1, &base);
   const int NB = d->NB;
-  const int per_step[FLAMED_DEN_KERNEL_CLASSES] = {1, NB + 1, 0, NB + 1, NB + 1, NB, NB, 1, fused ? 0 : 1};
+  const int per_step[FLAMED_DEN_KERNEL_CLASSES] = {1, NB + 1, 0, NB + 1, NB + 1, NB, NB, 1, p.fused() ? 0 : 1};  // (fused steps: no combine launch)
   for (int c = 0; c < FLAMED_DEN_KERNEL_CLASSES && rc == kOk; ++c) {
     float t = base;
     if (per_step[c] > 0 && (c != 2 || d->gcnt == nullptr)) rc = timed(c, &t);

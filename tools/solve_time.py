@@ -1,7 +1,8 @@
 """Time ProbGenerator solves (the denoiser's Euler loop) for given shapes under knob settings, e.g.
     python tools/solve_time.py --shapes 1x2400x256,2x400x128 --knobs persist=1 persist=0
-prints one line per (shape, knob set): median ms per solve over --reps timed solves after a warm one, whether
-the persistent launch ran, and whether the output equals (bitwise) the shape's first knob set's.
+prints one line per (shape, knob set): median ms per solve over --reps timed solves after a warm one (timed by
+itself: the first solve of a shape in the process, which on the launch path captures its graphs), whether the
+persistent launch ran, and whether the output equals (bitwise) the shape's first knob set's.
 --solver midpoint|heun runs the two-stage second-order solve instead (the shape's last number stays the count of
 velocity evaluations).  --make-ref FILE computes, on the CPU in fp32 with the module's own torch ops, a converged
 solution (midpoint, --ref-steps steps) of utterance 0 of the one given shape and stores it; --ref FILE then prints
@@ -75,8 +76,11 @@ def main():
             for k, v in kv:
                 nat.check(L.flamed_tune(k.encode(), int(v)), "tune")
             with torch.inference_mode():
-                ref = solve()
                 torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ref = solve()  # the warm one: on the launch path it captures the shape's graphs
+                torch.cuda.synchronize()
+                warm_ms = (time.perf_counter() - t0) * 1e3
                 r0 = hip.persist_status()[0]
                 times = []
                 for _ in range(a.reps):
@@ -98,7 +102,8 @@ def main():
                 err += f", rel-L2 of utterance 0 vs the converged solution {float(d.norm() / conv.norm()):.3e}"
             form = "" if lens is None else f" lens {a.lens} ({'each alone' if a.alone else 'exact lengths, one call'})"
             print(f"B={B} T={T} nfe={nfe} {a.solver}{form} [{kn or 'defaults'}]: {statistics.median(times):.2f} ms/solve "
-                  f"(min {min(times):.2f}), persistent launches {runs}/{a.reps}, finite {bool(torch.isfinite(ref).all())}, "
+                  f"(min {min(times):.2f}, the warm solve before them {warm_ms:.2f}), "
+                  f"persistent launches {runs}/{a.reps}, finite {bool(torch.isfinite(ref).all())}, "
                   f"equal to the first knob set {bool(torch.equal(ref, first))}"
                   f"{err}{chain_info(L, hip)}", flush=True)
             for k, _ in kv:  # back to the process defaults of the Tune struct

@@ -14,13 +14,16 @@ PVA, prior and prompt-side modules.  f32 and bf16 where the stage has both, grap
   pva_flow      launch and graph path (use_graph 0 and 3): dense (3, 13); exact (3, 13) 13/7/2, (4, 16) 16/15/1/9
   prior_decode  (2, 33, 32) target lengths 33/20: dense, and prompt lengths 32/31
   vq_encode     (2, 240): codes, quantized sum, speaker embedding
-  den_solve     (--denoiser) the graph of launches (`persist` knob 0): (B, T, nfe) = (1, 64, 4), (2, 37, 4)
+  den_solve     (--denoiser) the graph of launches (`persist` knob 0): (B, T, nfe) = (1, 64, 4), (2, 37, 4), (3, 37, 7)
+                (odd: no ping-pong fusion), (4, 400, 4) (large-M in-place fused steps); (2, 37, 8) in two parts
+                (flamed_den_solve_part, graph_steps 4); midpoint (2, 40, 8) f32 and (4, 400, 8) bf16; exact lengths
+                `tiny` and `large` of tests/test_ragged_launch_gpu.SHAPES, and `tiny` with ragged_launch 0
 
 The inputs and models come from the tests' helpers (tests/_faclens.py, _flamed_common.py, _xfmrprofile.py,
 test_prior_profile_gpu._decode_inputs, test_denoiser_gpu._prob_gen): a change to those changes the digests, so compare
 two libraries with one checkout of this tool and the tests, never digests recorded at different commits.  --denoiser
-sets the process knob `persist` to 0 and back to 1, its default (the library has no getter): run it in a process of its
-own, as above.
+sets the process knobs `persist`, `graph_steps` and `ragged_launch` and puts each back at its default (1, 16, 1: the
+library has no getter): run it in a process of its own, as above.
 """
 import argparse
 import hashlib
@@ -136,23 +139,63 @@ def vq_encode():
 def den_solve():
     from flamed import _native as nat
     from test_denoiser_gpu import _prob_gen
+    from test_exact_lengths_gpu import _inputs as lens_inputs, _ts
+    from test_ragged_launch_gpu import SHAPES
     L = nat.lib()
-    nat.check(L.flamed_tune(b"persist", 0), "flamed_tune")
+    tune = lambda key, v: nat.check(L.flamed_tune(key, v), "flamed_tune")
+    tune(b"persist", 0)
     try:
         for mode in ("f32", "bf16"):
             pg, _ = _prob_gen(mode)
-            for B, T, nfe in ((1, 64, 4), (2, 37, 4)):
+            hip = pg.denoiser.hip()
+
+            def inputs(B, T):
                 g = torch.Generator().manual_seed(1000 * B + T)
                 x0 = (0.3 * torch.randn(B, T, 256, generator=g) + torch.randn(B, T, 256, generator=g)).to(DEV)
-                spk = torch.randn(B, 256, generator=g).to(DEV)
-                ts = torch.linspace(0, 1, nfe + 1, device=DEV)
-                hip = pg.denoiser.hip()
-                hip.solve(x0, ts, spk, nfe)  # creates the handle
+                return x0, torch.randn(B, 256, generator=g).to(DEV)
+
+            def solves(label, fn):
+                hip._ensure(torch.device(DEV))  # creates the handle
                 r0 = hip.persist_status()[0]
-                both_graphs(pg.denoiser, f"den_solve {mode} ({B}, {T}, {nfe})", lambda: hip.solve(x0, ts, spk, nfe).clone())
+                both_graphs(pg.denoiser, f"den_solve {mode} {label}", lambda: fn().clone())
                 assert hip.persist_status()[0] == r0, "the solve took the persistent path"
+
+            # Euler: fused small-M steps, an odd step count (G = 7: no ping-pong fusion), large-M in-place fused steps
+            for B, T, nfe in ((1, 64, 4), (2, 37, 4), (3, 37, 7), (4, 400, 4)):
+                x0, spk = inputs(B, T)
+                solves(f"({B}, {T}, {nfe})", lambda: hip.solve(x0, torch.linspace(0, 1, nfe + 1, device=DEV), spk, nfe))
+            # a solve in two parts (flamed_den_solve_part), four steps per captured graph
+            B, T, nfe = 2, 37, 8
+            x0, spk = inputs(B, T)
+            r = torch.arange(nfe * B, device=DEV)
+            mods = hip.adaln(torch.linspace(0, 1, nfe + 1, device=DEV)[:nfe], spk, r // B, r % B)
+            ws = torch.empty(L.flamed_den_workspace_size(hip.handle, B, T), dtype=torch.uint8, device=DEV)
+            tune(b"graph_steps", 4)
+            try:
+                for use_graph in (1, 1, 0):
+                    x = x0.clone()
+                    for s0, s1 in ((0, 4), (4, 8)):
+                        nat.check(L.flamed_den_solve_part(hip.handle, nat.ptr(x), nat.ptr(mods), nfe, B, T, nat.ptr(ws), ws.numel(),
+                                                          use_graph, s0, s1, nat.stream_ptr(torch.device(DEV))), "flamed_den_solve_part")
+                    emit(f"den_solve {mode} ({B}, {T}, {nfe}) parts 0-4-8 graph={use_graph}", x)
+            finally:
+                tune(b"graph_steps", 16)
+            # RK2 (midpoint)
+            B, T = (2, 40) if mode == "f32" else (4, 400)
+            x0, spk = inputs(B, T)
+            solves(f"midpoint ({B}, {T}, 8)", lambda: hip.solve_rk2(x0, _ts(0.5), spk, 4, 0.5))
+            # exact lengths on the launch path, and one utterance after another (ragged_launch 0)
+            for name, ragged in (("tiny", 1), ("large", 1), ("tiny", 0)):
+                lens = SHAPES[name]
+                xl, sl = (t.to(DEV) for t in lens_inputs(lens))
+                tune(b"ragged_launch", ragged)
+                try:
+                    solves(f"lens {name} ragged_launch={ragged}", lambda: hip.solve(xl, _ts(None), sl, 8, lens=lens))
+                    assert hip.lens_path() == (2 if ragged else 3)
+                finally:
+                    tune(b"ragged_launch", 1)
     finally:
-        nat.check(L.flamed_tune(b"persist", 1), "flamed_tune")
+        tune(b"persist", 1)
 
 
 def main():
